@@ -1,6 +1,15 @@
 """BEAST hot-path benchmark on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--no-bpe] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--windows M] [--no-bpe] [--no-cpu] ...
+
+A plain run does what the headline needs and no more: set up, W warm-up steps, ONE timed window of
+exactly K steps (``ms_per_step`` = its wall clock / K, ``value`` = trajectories / its wall clock),
+the outputs of the last timed step if ``--dump-outputs DIR`` asks for them (``tokens.npy``,
+``params.npy``, ``positions.npy``: the same seeded inputs every run, so two builds can be compared
+array for array), and the JSON line.  ``--full`` adds every other leg described below (more timed
+windows, the host/GPU split, rooflines, MFMA utilisation, fit, BPE, CPU baselines, parity checks);
+in a plain run their objects in the line are null.
 
 One step = BEASTBsplineTokenizer.encode(x) -> reconstruct_traj(tokens) over one
 synthetic batch already resident in HBM (config "1xMI355X: num_dof=14
@@ -12,17 +21,19 @@ is the max over ranks.  rank 0 prints ONE JSON line.  At N > 1 the BPE leg times
 multi-rank trainer forms (replicated: one all-gather of the distinct words; sharded: a
 per-pass all-reduce of the pair-count deltas) and checks both against the K5 golden.
 
-``timing.host_issue_us_per_step`` / ``gpu_busy_us_per_step`` split a step into the host's
-cost of issuing it and the GPU's cost of running it (``host_issue_split``).
+With ``--full``, ``timing.host_issue_us_per_step`` / ``gpu_busy_us_per_step`` split a step into
+the host's cost of issuing it and the GPU's cost of running it (``host_issue_split``).
 
-Timing: W untimed warm-up steps, then ``--windows`` windows of exactly K steps, each
+Timing: W untimed warm-up steps, then ``--windows`` windows of exactly K steps (1 by default, so K
+is the number of timed steps; with ``--full`` enough windows for >= 2,000 steps, at least 5), each
 bracketed by barrier + device synchronize (wall clock from after the opening synchronize to the
 closing one, the barrier after it; max over ranks); ``value`` /
 ``ms_per_step`` come from the median window (one 20-step window is ~0.2 ms of wall clock:
-start-up jitter would dominate a single one).  Nothing else runs inside a timed window; the
-HIP-event times of the same windows are taken in separate, untimed windows.
+start-up jitter weighs on a single one, so a plain run wants a K of thousands).  Nothing else runs
+inside a timed window; the HIP-event times of the same windows are taken in separate, untimed
+windows (``--full``).
 
-Extra objects in that line:
+Extra objects in that line with ``--full``:
   roofline      dominant kernel: algorithmic bytes / its average launch duration measured live in
                 this run (HIP events around back-to-back launches on the kernel's stream); `traffic`
                 is the PMC HBM bytes per launch of the same-tree profile summary
@@ -93,9 +104,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: more timed windows, HIP-event and host/GPU splits, "
+                         "rooflines, MFMA utilisation, fit_parameters (K4), BPE (K5), CPU baselines and parity "
+                         "checks (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (tokens, params, "
+                         "positions) as DIR/<name>.npy")
     ap.add_argument("--windows", type=int, default=None,
-                    help="timed windows of --steps steps (median reported); default: enough for >= 2,000 timed "
-                         "steps, at least 5")
+                    help="timed windows of --steps steps (median reported); default 1, so that --steps is the "
+                         "number of timed steps; with --full enough for >= 2,000 timed steps, at least 5")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--no-bpe", action="store_true")
     ap.add_argument("--no-bpe-api", action="store_true", help="skip the fit_from_trajectories API leg")
@@ -114,7 +132,36 @@ def parse():
                     help="same-tree profile summary (tools/make_profile_summary.py): rocprofv3 kernel averages of "
                          "this command and PMC bytes / MFMA counts per launch; used only when its library "
                          "fingerprint equals this tree's")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET = 63 * 1000 * 1000   # bytes of all the --dump-outputs arrays together (64 MB with headroom)
+
+
+def dump_outputs(path: str, outputs: dict) -> dict:
+    """--dump-outputs: what the last timed step returned to its caller, one ``<name>.npy`` each
+    (integers as float64, floats in their own width).  Every array has one row per trajectory;
+    beyond DUMP_BUDGET bytes the same fixed, seeded sample of rows is written of each, with the
+    row numbers beside them (``sample_rows.npy``)."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    B = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(B, 1) for a in host.values()) + 8
+    rows = None
+    if B * row_bytes > DUMP_BUDGET:
+        rows = np.sort(np.random.default_rng(0).choice(B, size=DUMP_BUDGET // row_bytes, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": {name: list(a.shape) for name, a in host.items()},
+            "bytes": int(sum(a.nbytes for a in host.values())), "rows_sampled": rows is not None}
 
 
 def host_info() -> dict:
@@ -816,7 +863,7 @@ def dump_k5(dev, args):
 def main():
     args = parse()
     if args.windows is None:
-        args.windows = max(5, -(-2000 // max(args.steps, 1)))
+        args.windows = max(5, -(-2000 // max(args.steps, 1))) if args.full else 1
     torch.set_num_threads(_host_threads())
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -849,6 +896,10 @@ def main():
         tokens, _ = tok.encode(x)
         return tok.reconstruct_traj(tokens)
 
+    def step_kept():   # the same step, its results kept: the last one of a window (--dump-outputs)
+        tokens, pd = tok.encode(x)
+        return tokens, pd, tok.reconstruct_traj(tokens)
+
     for _ in range(args.warmup):
         step()
     # the timed windows hold the K steps and nothing else: HIP events recorded inside a window cost
@@ -861,53 +912,60 @@ def main():
     for _ in range(max(args.windows, 1)):
         sync(world)
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        tokens, pd, pos = step_kept()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         sync(world)
         walls.append(max_over_ranks(t1 - t0, world, dev))
     el = float(np.median(walls))
-    gpu_ms = []
-    for _ in range(5):   # untimed: the same windows with HIP events on the kernels' stream
-        sync(world)
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record(stream)
-        for _ in range(args.steps):
-            step()
-        e_ev.record(stream)
-        sync(world)
-        gpu_ms.append(max_over_ranks(s_ev.elapsed_time(e_ev), world, dev))
     value = B * world * args.steps / el
-    split = host_issue_split(step, stream, args.steps)
-    gpu_tokens = tok.encode(x)[0].cpu().numpy()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"tokens": tokens, "params": pd["params"], "positions": pos})
+    del tokens, pd, pos
 
-    # ---- dominant-kernel roofline: the same-tree rocprofv3 average when the profile matches this
-    #      tree, HIP events measured live on the kernel's stream beside it
-    prof, prof_note = load_profile(args.profile)
-    RANK_INFO["profile"] = prof
-    launch_enc, launch_rec = launchers(tok, dev, stream, x, B)
-    t_enc = kernel_time_us(launch_enc, stream)
-    t_rec = kernel_time_us(launch_rec, stream)
-    roof = codec_roofline(prof, prof_note, t_enc, t_rec, B)
-    times_us = {"encode_4096": t_enc}
-    if not args.no_large:
-        roof["large_batch"] = lb = large_batch_roofline(tok, dev, stream, args.large_batch)
-        lb["duration_source"] = "HIP events (rocprof's average for these instantiations mixes fit_parameters' launches)"
-    mfma = mfma_utilisation(prof, prof_note, times_us)
+    # a plain run ends here; everything below the headline is --full's
+    gpu_ms, split, roof, mfma, fitb, bpe, cpu, parity = None, {}, None, None, None, None, None, None
+    if args.full:
+        gpu_ms = []
+        for _ in range(5):   # untimed: the same windows with HIP events on the kernels' stream
+            sync(world)
+            s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s_ev.record(stream)
+            for _ in range(args.steps):
+                step()
+            e_ev.record(stream)
+            sync(world)
+            gpu_ms.append(max_over_ranks(s_ev.elapsed_time(e_ev), world, dev))
+        split = host_issue_split(step, stream, args.steps)
+        gpu_tokens = tok.encode(x)[0].cpu().numpy()
 
-    fitb = None
-    if not args.no_fit:
-        fitb = fit_bench(dev, args, world, rank)
+        # ---- dominant-kernel roofline: the same-tree rocprofv3 average when the profile matches this
+        #      tree, HIP events measured live on the kernel's stream beside it
+        prof, prof_note = load_profile(args.profile)
+        RANK_INFO["profile"] = prof
+        launch_enc, launch_rec = launchers(tok, dev, stream, x, B)
+        t_enc = kernel_time_us(launch_enc, stream)
+        t_rec = kernel_time_us(launch_rec, stream)
+        roof = codec_roofline(prof, prof_note, t_enc, t_rec, B)
+        times_us = {"encode_4096": t_enc}
+        if not args.no_large:
+            roof["large_batch"] = lb = large_batch_roofline(tok, dev, stream, args.large_batch)
+            lb["duration_source"] = "HIP events (rocprof's average for these instantiations mixes fit_parameters' " \
+                                    "launches)"
+        mfma = mfma_utilisation(prof, prof_note, times_us)
 
-    bpe = None
-    if not args.no_bpe:
-        bpe = bpe_bench(dev, args, world, rank, reduce, prof, prof_note)
+        if not args.no_fit:
+            fitb = fit_bench(dev, args, world, rank)
 
-    cpu, parity = None, None
-    if rank == 0 and not args.no_cpu:
-        cpu, parity = cpu_baseline(x_np, gpu_tokens, (tok.w_min.cpu().numpy(), tok.w_max.cpu().numpy()),
-                                   args.cpu_seconds)
+        if not args.no_bpe:
+            bpe = bpe_bench(dev, args, world, rank, reduce, prof, prof_note)
+
+        if rank == 0 and not args.no_cpu:
+            cpu, parity = cpu_baseline(x_np, gpu_tokens, (tok.w_min.cpu().numpy(), tok.w_max.cpu().numpy()),
+                                       args.cpu_seconds)
 
     if rank == 0:
         line = {
@@ -920,8 +978,9 @@ def main():
                                    "seq_len=50 vocab=256 degree_p=4", "global_batch": B * world,
                        "per_gpu_batch": B, "seq_len": T, "parallelism": f"dp{world}"},
             "timing": {"windows": len(walls), "window_wall_s": walls, "window_gpu_event_ms": gpu_ms,
-                       "median_gpu_event_us_per_step": float(np.median(gpu_ms)) / args.steps * 1e3,
+                       "median_gpu_event_us_per_step": float(np.median(gpu_ms)) / args.steps * 1e3 if gpu_ms else None,
                        "wall_us_per_step": el / args.steps * 1e6, **split},
+            "full": args.full, "outputs": dumped,
             "roofline": roof, "mfma": mfma, "cpu_baseline": cpu, "token_parity": parity,
             "host": host_info(), "fit": fitb, "bpe": bpe,
             "dist": {"world_size": world, "backend": torch.distributed.get_backend() if world > 1 else None,

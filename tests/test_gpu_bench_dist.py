@@ -22,8 +22,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 
 FIT_TRAJS, BPE_SEQS, BPE_VOCAB = 65536, 16384, 1024
-ARGS = ["bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--windows", "2", "--no-cpu", "--no-large",
-        "--no-bpe-api", "--fit-trajs", str(FIT_TRAJS), "--bpe-seqs", str(BPE_SEQS), "--bpe-vocab", str(BPE_VOCAB)]
+ARGS = ["bench.py", "--full", "--gpus", "2", "--steps", "5", "--warmup", "2", "--windows", "2", "--no-cpu",
+        "--no-large", "--no-bpe-api", "--fit-trajs", str(FIT_TRAJS), "--bpe-seqs", str(BPE_SEQS), "--bpe-vocab", str(BPE_VOCAB)]
 
 
 def _free_port():
@@ -114,7 +114,7 @@ def test_bench_gpus_2_spawns_its_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env.update({"BEAST_BENCH_ONE_DEVICE": "1", "BEAST_BENCH_BACKEND": "gloo"})
-    args = ["--gpus", "2", "--steps", "5", "--warmup", "2", "--windows", "2", "--no-cpu", "--no-large",
+    args = ["--full", "--gpus", "2", "--steps", "5", "--warmup", "2", "--windows", "2", "--no-cpu", "--no-large",
             "--no-bpe-api", "--fit-trajs", "65536"]
     r = subprocess.run([sys.executable, "-u", os.path.join(REPO, "bench.py"), *args], env=env, cwd=REPO,
                        capture_output=True, text=True, timeout=280)

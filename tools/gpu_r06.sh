@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-6 GPU session steps (one box).  bash tools/gpu_r06.sh TAG STEP...
 #   tests:<pytest args>   pytest -m gpu on the given files / -k expression
-#   bench                 python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command)
+#   bench                 python bench.py --full --gpus 1 --steps 20 --warmup 5 (every leg of the bench)
 #   hostsplit             tools/host_split.py and the launch-cost microbenchmark
 #   smoke                 __graft_entry__.smoke()
 # Each step has its own time limit; the first failing step ends the script.
@@ -21,7 +21,7 @@ for st in "$@"; do
       timeout -k 10 900 python -u -m pytest $sel -m gpu -x -v --timeout 300 --timeout-method thread > "$O/pytest_$n.log" 2>&1
       rc=$?; echo "tests[$sel] rc=$rc"; tail -n 3 "$O/pytest_$n.log" ;;
     bench)
-      timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_$n.json" 2> "$O/bench_$n.err"
+      timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_$n.json" 2> "$O/bench_$n.err"
       rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || tail -n 8 "$O/bench_$n.err"
       python - "$O/bench_$n.json" <<'EOF' || true
 import json, sys
@@ -35,7 +35,7 @@ print("bpe", b.get("value"), b.get("setup_s"), b.get("merge_loop_s"), (b.get("co
 EOF
       ;;
     bench2)
-      timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu > "$O/bench2_$n.json" 2> "$O/bench2_$n.err"
+      timeout -k 10 600 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu > "$O/bench2_$n.json" 2> "$O/bench2_$n.err"
       rc=$?; echo "bench2 rc=$rc"; [ $rc -eq 0 ] || tail -n 8 "$O/bench2_$n.err" ;;
     hostsplit)
       timeout -k 10 300 python tools/host_split.py > "$O/host_split_$n.json" 2>&1

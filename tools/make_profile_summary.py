@@ -3,8 +3,8 @@
     python tools/make_profile_summary.py OUT.json --stats STATS.csv [--codec-pmc DIR] [--bpe-pmc DIR]
                                          [--bench BENCH.json] [--head SHA]
 
-  --stats      rocprofv3 --kernel-trace --stats summary (kernel_stats.csv) of `python bench.py`, the
-               driver's own command: each kernel's average launch duration under the profiler
+  --stats      rocprofv3 --kernel-trace --stats summary (kernel_stats.csv) of `python bench.py --full`
+               (every leg of the bench): each kernel's average launch duration under the profiler
   --codec-pmc  tools/gpu_pmc.sh output (FETCH_SIZE and WRITE_SIZE passes over tools/pmc_codec.py at
                B = 4,096): HBM bytes per launch of k_encode_v / k_reconstruct_v
   --bpe-pmc    tools/bpe_pmc.sh output (FETCH_SIZE / WRITE_SIZE over tools/bpe_profile.py at K5):
