@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -28,6 +28,11 @@ OPT_MERGE_LDS_MIN = 3
 OPT_BPE_ENCODE_MODE = 5
 OPT_BPE_DEDUP_KEY_BITS = 6
 OPT_BPE_TRAIN_HOST_LOOP = 7
+OPT_LAST_CODEC_LAUNCH = 8   # read-only
+
+# kernel families of OPT_LAST_CODEC_LAUNCH (bits 0-3), in the header's order
+CODEC_FAMILIES = (None, "encode_v", "encode_spec", "encode_dyn", "reconstruct_v", "reconstruct_spec",
+                  "reconstruct_mfma", "reconstruct_rows")
 
 _vp, _i64, _i32, _f32, _f64, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t
 
@@ -169,6 +174,31 @@ def call(name: str, *args) -> int:
 def run(name: str, *args) -> None:
     """Call a status-returning entry point and raise on failure."""
     check(call(name, *args), name)
+
+
+class CodecLaunch(NamedTuple):
+    """Decoded BEAST_OPT_LAST_CODEC_LAUNCH (include/beast_hip.h): the kernel the last encode /
+    reconstruct launch of this process chose."""
+    family: Optional[str]   # one of CODEC_FAMILIES; None before any launch
+    tile: int               # trajectories per tile
+    waves: int              # waves per workgroup
+    ks: int                 # MFMA K-steps over the basis functions (reconstruct)
+    fast: bool              # encode input by contiguous DMA
+    basis_regs: bool        # reconstruct basis operands in registers
+    staged: bool            # output staged through LDS
+    latency: bool           # latency variant (write-through stores) rather than the bulk one
+    raw: int
+
+
+def decode_codec_launch(v: int) -> CodecLaunch:
+    fam = v & 15
+    return CodecLaunch(CODEC_FAMILIES[fam] if fam < len(CODEC_FAMILIES) else None, (v >> 4) & 31, (v >> 9) & 31,
+                       (v >> 14) & 7, bool(v >> 17 & 1), bool(v >> 18 & 1), bool(v >> 19 & 1), bool(v >> 20 & 1), v)
+
+
+def last_codec_launch() -> CodecLaunch:
+    """The kernel choice of this process's last encode / reconstruct launch (tests, tools)."""
+    return decode_codec_launch(load().beast_get_option(OPT_LAST_CODEC_LAUNCH))
 
 
 def ptr(t: Optional[torch.Tensor]):

@@ -957,6 +957,10 @@ __global__ __launch_bounds__(S::W * 64) void k_reconstruct(const void* __restric
   STAMP(1, 11);
   for (int t = tid; t < a.lut_n; t += NT) lut[t] = __fdiv_rn((float)t, vm1);
   STAMP(1, 12);
+  // num_dof_out > D: the output columns dof_dst does not name are zeros (as k_reconstruct_rows
+  // writes them).  The MFMA loop never touches them, so the image is cleared once.
+  if (ndo > D)
+    for (int i = tid; i < TBT * RTR * ndo; i += NT) ob[i] = 0.0f;
 
   for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     const int64_t b0 = tile * TBT;
@@ -1371,6 +1375,20 @@ bool wide_blocks(int64_t ntiles) {
 // the per-trajectory kernels at any batch size.
 bool enc_v() { return g_block_waves == 0 || g_block_waves == 8; }
 
+// BEAST_OPT_LAST_CODEC_LAUNCH (tests, tools): which kernel the last encode / reconstruct launch of
+// this process chose, packed as include/beast_hip.h lays out.  Every launcher stores it once,
+// relaxed, after its LDS check and before the launch; 0 until the first launch.
+std::atomic<int> g_last_launch{0};
+enum LaunchFamily {
+  FAM_ENCODE_V = 1, FAM_ENCODE_SPEC = 2, FAM_ENCODE_DYN = 3, FAM_REC_V = 4, FAM_REC_SPEC = 5, FAM_REC_MFMA = 6,
+  FAM_REC_ROWS = 7
+};
+constexpr int launch_mark(int family, int tile, int waves, int ks, bool fast, bool regs, bool staged, bool lat) {
+  return family | tile << 4 | waves << 9 | ks << 14 | (fast ? 1 << 17 : 0) | (regs ? 1 << 18 : 0) |
+         (staged ? 1 << 19 : 0) | (lat ? 1 << 20 : 0);
+}
+inline void mark_launch(int v) { g_last_launch.store(v, std::memory_order_relaxed); }
+
 // Host launch of a hot kernel through hipModuleLaunchKernel with a cached function handle (per
 // device): the runtime skips hipLaunchKernel's host-function lookup and the GGL template's
 // argument packing, ≈0.15 us of host time per launch (profiles/r02/launch_host_cost.json).
@@ -1399,11 +1417,12 @@ int launch_fn(const void* kernel, std::atomic<hipFunction_t> (&cache)[16], unsig
 }
 
 template <class S, int W, int SP>
-int launch_encode_vw(EncArgs a, hipStream_t s) {
+int launch_encode_vw(EncArgs a, bool lat, hipStream_t s) {
   constexpr EvSmem L = ev_smem<S, W>(S::NJ < S::D ? 2 : 1);
   static_assert(L.total <= (W <= 8 ? 80 : 160) * 1024, "k_encode_v LDS");
   a.g = make_geom<W>(S::D, S::NJ, S::N, S::T);
   a.ntiles = (a.B + W - 1) / W;
+  mark_launch(launch_mark(FAM_ENCODE_V, W, W, 0, true, false, true, lat));
   static std::atomic<hipFunction_t> fn[16] = {};
   return launch_fn(reinterpret_cast<const void*>(&k_encode_v<S, SP, W>), fn, (unsigned)a.ntiles, W * 64, L.total, s,
                    "k_encode_v", a.traj, a.B,
@@ -1416,7 +1435,7 @@ int launch_encode_vw(EncArgs a, hipStream_t s) {
 template <class S>
 int launch_encode_v(EncArgs a, hipStream_t s) {
   const bool lat = a.B <= 16 * (int64_t)cu_count();
-  return lat ? launch_encode_vw<S, RV_WE, LAT_SP>(a, s) : launch_encode_vw<S, RV_WE_BULK, 0>(a, s);
+  return lat ? launch_encode_vw<S, RV_WE, LAT_SP>(a, true, s) : launch_encode_vw<S, RV_WE_BULK, 0>(a, false, s);
 }
 
 template <int TBT, class S>
@@ -1427,15 +1446,29 @@ int launch_encode_t(EncArgs a, int T, int D, int nj, int N, bool fast, hipStream
   const EncSmem L = enc_smem<TBT>(T, a.g.Tp, Dl, D, N, nj < D ? 2 : 1);
   BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "encode tile needs %d B of LDS", L.total);
   const int64_t grid = grid_for(a.ntiles, L.total);
+  mark_launch(launch_mark(S::fixed ? FAM_ENCODE_SPEC : FAM_ENCODE_DYN, TBT, S::W, 0, fast, false, true, S::W == 7));
   if (fast) hipLaunchKernelGGL((k_encode<TBT, true, S>), dim3(grid), dim3(S::W * 64), L.total, s, a);
   else hipLaunchKernelGGL((k_encode<TBT, false, S>), dim3(grid), dim3(S::W * 64), L.total, s, a);
   BEAST_LAUNCHED("k_encode");
   return BEAST_OK;
 }
 
+int enc_smem_total(int tbt, int T, int Dl, int D, int N, int nkinds) {
+  const int Tp = round_up(T, 4);
+  switch (tbt) {
+    case 1: return enc_smem<1>(T, Tp, Dl, D, N, nkinds).total;
+    case 2: return enc_smem<2>(T, Tp, Dl, D, N, nkinds).total;
+    case 4: return enc_smem<4>(T, Tp, Dl, D, N, nkinds).total;
+    default: return enc_smem<8>(T, Tp, Dl, D, N, nkinds).total;
+  }
+}
+
 // Tile size: the largest of 8/4/2/1 trajectories whose rows fit 32 KB of LDS
-// (BEAST_ENC_TBT overrides, for measurements).  The BEAST default shapes (T = 50,
-// N = 10, D = 14 with 0 or 2 gripper DoF, D = 7) run fully specialised kernels.
+// (BEAST_ENC_TBT overrides, for measurements).  Rows the contiguous DMA path does not take
+// (strided, misaligned, or one trajectory above 32 KB) are gathered into [T][D] images by the
+// kernel: the largest tile whose whole LDS layout fits (one trajectory at T = 256, D = 64).
+// The BEAST default shapes (T = 50, N = 10, D = 14 with 0 or 2 gripper DoF, D = 7) run fully
+// specialised kernels.
 int launch_encode(EncArgs a, int T, int D, int nj, int N, hipStream_t s) {
   const int64_t traj_bytes = (int64_t)T * a.row_elems * 4;
   const bool contiguous = a.sd == 1 && a.st == a.row_elems && a.sb == (int64_t)T * a.row_elems &&
@@ -1447,7 +1480,10 @@ int launch_encode(EncArgs a, int T, int D, int nj, int N, hipStream_t s) {
   int tbt = 8;
   while (tbt > 1 && tbt * traj_bytes > 32 * 1024) tbt >>= 1;
   const bool fast = contiguous && tbt * traj_bytes <= 32 * 1024;
-  if (!fast) tbt = 8;
+  if (!fast) {
+    tbt = 8;
+    while (tbt > 1 && enc_smem_total(tbt, T, D, D, N, nj < D ? 2 : 1) > 160 * 1024) tbt >>= 1;
+  }
   if (forced == 1 || forced == 2 || forced == 4 || (forced == 8 && fast)) tbt = std::min(tbt, forced);
   // list mode: the contiguous DMA path only, tiles of one batch each
   BEAST_REQUIRE(!a.traj_list || (fast && a.list_rows % tbt == 0),
@@ -1481,6 +1517,9 @@ int launch_rec_ks(RecArgs a, int D, int nj, hipStream_t s) {
   const RecSmem L = rec_smem<TBT, KS, RT>(a.Tout, D, a.g.N, a.ndo, nj < D ? 2 : 1, a.lut_n);
   BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "reconstruct tile needs %d B of LDS", L.total);
   const int64_t grid = grid_for(a.ntiles, L.total);
+  mark_launch(KS == 0 ? launch_mark(FAM_REC_ROWS, TBT, NWAVES, 0, false, false, L.stage, false)
+                      : launch_mark(S::fixed ? FAM_REC_SPEC : FAM_REC_MFMA, TBT, S::W, KS, false, RT > 0, true,
+                                    S::W == 7));
   if constexpr (KS == 0) hipLaunchKernelGGL((k_reconstruct_rows<TBT>), dim3(grid), dim3(NTHREADS), L.total, s, a);
   else {
     static std::atomic<hipFunction_t> fn[16] = {};
@@ -1520,6 +1559,7 @@ int launch_rec_v(RecArgs a, hipStream_t s) {
   a.ntiles = (a.B + RV_WR - 1) / RV_WR;
   static std::atomic<hipFunction_t> fn[2][16] = {};
   const bool lat = a.B <= 16 * (int64_t)cu_count();   // <= 2 eight-trajectory tiles per CU
+  mark_launch(launch_mark(FAM_REC_V, RV_WR, RV_WR, KS, false, true, true, lat));
   return launch_fn(lat ? reinterpret_cast<const void*>(&k_reconstruct_v<KS, S, LAT_SP>)
                        : reinterpret_cast<const void*>(&k_reconstruct_v<KS, S, 0>),
                    fn[lat ? 1 : 0], (unsigned)a.ntiles, RV_WR * 64, L.total, s, "k_reconstruct_v",
@@ -1668,6 +1708,7 @@ extern "C" int beast_set_option(int option, int value) {
     beast::g_bpe_train_host = value;
     return BEAST_OK;
   }
+  BEAST_REQUIRE(option != BEAST_OPT_LAST_CODEC_LAUNCH, "BEAST_OPT_LAST_CODEC_LAUNCH is read-only");
   BEAST_REQUIRE(false, "unknown option %d", option);
   return BEAST_E_INVALID;
 }
@@ -1679,6 +1720,7 @@ extern "C" int beast_get_option(int option) {
   if (option == BEAST_OPT_BPE_ENCODE_MODE) return beast::g_bpe_encode_mode;
   if (option == BEAST_OPT_BPE_DEDUP_KEY_BITS) return beast::g_bpe_dedup_key_bits;
   if (option == BEAST_OPT_BPE_TRAIN_HOST_LOOP) return beast::g_bpe_train_host;
+  if (option == BEAST_OPT_LAST_CODEC_LAUNCH) return g_last_launch.load(std::memory_order_relaxed);
   beast::set_error("unknown option %d", option);
   return BEAST_E_INVALID;
 }

@@ -58,6 +58,18 @@ const char* beast_last_error(void);
  * match keeps them apart (same ids).
  * BEAST_OPT_BPE_TRAIN_HOST_LOOP = 1 (tests): beast_bpe_train runs the host-driven loop at any Vt;
  * 2 reruns it after the batched loop as a string-hash collision would.  Results are identical.
+ * BEAST_OPT_LAST_CODEC_LAUNCH (tests, tools; read-only: beast_set_option returns BEAST_E_INVALID):
+ * which kernel the last beast_encode_f32 / beast_encode_list_f32 / beast_reconstruct_f32 launch of
+ * this process chose, 0 before any launch.  Packed:
+ *   bits  0-3   kernel family: 1 k_encode_v, 2 k_encode specialised, 3 k_encode runtime-shape,
+ *               4 k_reconstruct_v, 5 k_reconstruct specialised, 6 k_reconstruct runtime-shape (MFMA),
+ *               7 k_reconstruct_rows
+ *   bits  4-8   trajectories per tile          bits 9-13  waves per workgroup
+ *   bits 14-16  KS, MFMA K-steps over the basis functions (reconstruct; 0 otherwise)
+ *   bit 17      encode input by contiguous DMA (0: gathered through the strides)
+ *   bit 18      reconstruct basis operands in registers (0: in LDS, or read per row from memory)
+ *   bit 19      output staged through LDS (0 only for k_reconstruct_rows' direct stores)
+ *   bit 20      latency variant (write-through stores, one tile per CU) rather than the bulk one
  * Options are process-wide and not synchronised: set them before launching, not concurrently. */
 #define BEAST_OPT_GENERIC_KERNELS 1
 #define BEAST_OPT_BLOCK_WAVES 2
@@ -65,6 +77,7 @@ const char* beast_last_error(void);
 #define BEAST_OPT_BPE_ENCODE_MODE 5
 #define BEAST_OPT_BPE_DEDUP_KEY_BITS 6
 #define BEAST_OPT_BPE_TRAIN_HOST_LOOP 7
+#define BEAST_OPT_LAST_CODEC_LAUNCH 8
 int beast_set_option(int option, int value);
 /* the option's current value (BEAST_E_INVALID for an unknown option) */
 int beast_get_option(int option);
@@ -100,7 +113,8 @@ int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, d
  *   params_out  [B][D*N] fp32 unclamped fit (params_dict['params']); nullable
  *   tokens_out  [B][N*D] int64 = round_half_even(clamp01((clamp(p)-wmin)/max(wmax-wmin,1e-8))*(vocab-1))
  *               + tok_offset; nullable.  vocab <= 0 disables quantisation.
- * Constraints: N <= 16, T <= 256, D <= 64. */
+ * Constraints: N <= 16, T <= 256, D <= 64; every shape inside them encodes, at any strides and
+ * alignment (16-byte aligned contiguous rows of at most 32 KB per trajectory take the DMA path). */
 int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st, int64_t sd, int row_elems,
                      int D, int n_joint, const int32_t* dof_src, const float* proj, int N,
                      const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
@@ -132,7 +146,8 @@ int beast_quantize_f32(const float* params, int64_t B, int D, int N, const float
  * and the scatter to joint/gripper columns (:520-534).
  *   tokens      [B][N*D] int64 (tok_offset is SUBTRACTED first)
  *   basis       [2][T_out][N] fp32 per kind; batch stride basis_sb (0 = shared)
- *   dof_dst     [D] output column of each DoF; pos_out [B][T_out][num_dof_out]
+ *   dof_dst     [D] output column of each DoF (D distinct columns); pos_out [B][T_out][num_dof_out],
+ *               num_dof_out >= D: the columns dof_dst does not name are written as 0
  *   init_p      nullable [B] rows of stride init_p_sb; init_p_src[d] column for
  *               joint DoF d (< n_joint)
  *   params_out  nullable [B][D*N] decoded params (= decode()); pos_out nullable.

@@ -173,6 +173,43 @@ def test_options_validate_and_reset():
     assert b"option" in lib.beast_last_error()
 
 
+def test_option_constants_match_header():
+    """Every BEAST_OPT_* of include/beast_hip.h has the same value as _lib.OPT_*, and vice versa."""
+    defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define BEAST_OPT_(\w+) (\d+)", open(HEADER).read())}
+    consts = {k[4:]: v for k, v in vars(_lib).items() if k.startswith("OPT_")}
+    assert defs == consts
+    assert defs["LAST_CODEC_LAUNCH"] == 8
+
+
+def test_last_codec_launch_is_read_only_and_zero_before_any_launch():
+    """BEAST_OPT_LAST_CODEC_LAUNCH reads 0 in a process that has launched nothing (a fresh one: this
+    process may have run GPU tests), decodes to an empty record, and beast_set_option refuses it."""
+    import sys
+    code = ("from beast_tokenizer_amd import _lib; lib = _lib.load(); "
+            "print(lib.beast_get_option(_lib.OPT_LAST_CODEC_LAUNCH), _lib.last_codec_launch().family)")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == ["0", "None"]
+    lib = _lib.load()
+    before = lib.beast_get_option(_lib.OPT_LAST_CODEC_LAUNCH)
+    assert before >= 0
+    for v in (0, 1, before):
+        assert lib.beast_set_option(_lib.OPT_LAST_CODEC_LAUNCH, v) == _lib.BEAST_E_INVALID
+        assert b"read-only" in lib.beast_last_error()
+    assert lib.beast_get_option(_lib.OPT_LAST_CODEC_LAUNCH) == before
+
+
+def test_codec_launch_decoder_fields():
+    """_lib.decode_codec_launch unpacks the header's bit layout."""
+    v = 6 | 8 << 4 | 4 << 9 | 3 << 14 | 1 << 18 | 1 << 19
+    m = _lib.decode_codec_launch(v)
+    assert m == ("reconstruct_mfma", 8, 4, 3, False, True, True, False, v)
+    m = _lib.decode_codec_launch(1 | 16 << 4 | 16 << 9 | 1 << 17 | 1 << 19 | 1 << 20)
+    assert (m.family, m.tile, m.waves, m.ks, m.fast, m.basis_regs, m.staged, m.latency) == \
+        ("encode_v", 16, 16, 0, True, False, True, True)
+    assert len(_lib.CODEC_FAMILIES) == 8 and _lib.decode_codec_launch(0).family is None
+
+
 def test_encode_list_validation():
     lib = _lib.load()
     fake = C.c_void_p(16)                   # never dereferenced: validation fails first
