@@ -43,6 +43,7 @@ SIGNATURES = {
     "beast_set_option": (_i32, [_i32, _i32]),
     "beast_get_option": (_i32, [_i32]),
     "beast_bspline_basis_f32": (_i32, [_vp, _i64, _f32, _f32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "beast_bspline_basis_deriv_f32": (_i32, [_vp, _i64, _f32, _f32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "beast_bspline_projection_f64": (_i32, [_vp, _i32, _i32, _f64, _vp, _vp]),
     "beast_encode_f32": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp,
                                 _i32, _i64, _vp, _vp, _vp]),
@@ -53,6 +54,8 @@ SIGNATURES = {
     "beast_cond_add_f32": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "beast_reconstruct_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32,
                                      _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "beast_reconstruct_derivs_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp,
+                                            _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "beast_colminmax_workspace_bytes": (_sz, [_i64, _i32]),
     "beast_colminmax_f32": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
     "beast_quantile_workspace_bytes": (_sz, [_i64, _i32, _i32]),

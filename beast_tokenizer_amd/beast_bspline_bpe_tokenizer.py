@@ -258,6 +258,20 @@ class BEASTBsplineBPETokenizer(BEASTBsplineTokenizer):
         # the reference takes MP tokens here, not BPE ids (its BPE decode line is commented out)
         return super().reconstruct_traj(tokens, times=times, **kwargs)
 
+    # velocity / acceleration: MP tokens, exactly as reconstruct_traj takes them (BPE ids go
+    # through bpe_to_mp_tokens first)
+    def reconstruct_traj_derivs(self, tokens: Iterable[TokenLike], times: Optional[torch.Tensor] = None,
+                                orders=(0, 1, 2), **kwargs) -> tuple:
+        return super().reconstruct_traj_derivs(tokens, times=times, orders=orders, **kwargs)
+
+    def reconstruct_traj_vel(self, tokens: Iterable[TokenLike], times: Optional[torch.Tensor] = None,
+                             **kwargs) -> torch.Tensor:
+        return super().reconstruct_traj_vel(tokens, times=times, **kwargs)
+
+    def reconstruct_traj_acc(self, tokens: Iterable[TokenLike], times: Optional[torch.Tensor] = None,
+                             **kwargs) -> torch.Tensor:
+        return super().reconstruct_traj_acc(tokens, times=times, **kwargs)
+
     # ------------------------------------------------------------------ serialisation
 
     def get_config(self):  # type: ignore[override]

@@ -204,6 +204,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         self._conditioned = self._basis.conditioned and self.joint_dof > 0
         self._cond_state = None
         self._full_basis = {}
+        self._full_deriv = {}
         self._times_version = 0
         # tensor_linspace(0, duration, seq_len) == torch.linspace in fp32 (util_matrix.py:114-116)
         self.times = torch.linspace(0, duration, seq_len).to(device)
@@ -381,9 +382,11 @@ class BEASTBsplineTokenizer(TokenizerBase):
             return {"init_pos": None, "init_vel": None, "end_pos": None, "end_vel": None}
         return {k: st[k] for k in ("init_pos", "init_vel", "end_pos", "end_vel")}
 
-    def _add_conditions(self, pos: torch.Tensor, times, B: int, dev: torch.device) -> torch.Tensor:
+    def _add_conditions(self, pos: torch.Tensor, times, B: int, dev: torch.device, order: int = 0) -> torch.Tensor:
         """pos[..., joints] += boundary control points' term + init_pos (get_traj_pos with the
-        last fit's conditions, uni_bspline.py:126-166)."""
+        last fit's conditions, uni_bspline.py:126-166).  ``order`` 1 / 2: the same term of the
+        order-th time derivative -- that order's full derivative basis, and zeros for init_pos
+        (the constant offset differentiates away)."""
         st = self._cond_state
         if st is None:
             raise RuntimeError("reconstruct with init/end conditions needs the conditions of a previous "
@@ -395,12 +398,20 @@ class BEASTBsplineTokenizer(TokenizerBase):
         if sdev != dev:   # the kernel reads these raw pointers on dev: refuse as ATen's einsum did
             raise RuntimeError(f"Expected all tensors to be on the same device, but found at least two devices, "
                                f"{sdev} and {dev}! (boundary conditions were fitted on {sdev})")
-        if times is None:
+        if times is None and order:
+            key = (dev, self._times_version, order)
+            full = self._full_deriv.get(key)
+            if full is None:
+                self._full_deriv = {k: v for k, v in self._full_deriv.items() if k[:2] == key[:2]}
+                full = self._full_deriv[key] = self._basis.full_deriv_basis_at(self.times.to(dev).reshape(-1), order)
+        elif times is None:
             key = (dev, self._times_version)
             full = self._full_basis.get(key)
             if full is None:
                 self._full_basis = {key: self._basis.full_basis_at(self.times.to(dev).reshape(-1))}
                 full = self._full_basis[key]
+        elif order:
+            full = self._basis.full_deriv_basis_at(times.to(dev, dtype=torch.float32), order).contiguous()
         else:   # [T] or per-row [B, T] grids -> [T, C] / [B, T, C]
             full = self._basis.full_basis_at(times.to(dev, dtype=torch.float32)).contiguous()
         if full.dim() not in (2, 3) or full.shape[-2] != pos.shape[1]:
@@ -409,7 +420,8 @@ class BEASTBsplineTokenizer(TokenizerBase):
         _lib.run("beast_cond_add_f32", pos.data_ptr(), B, pos.shape[1], pos.shape[2], jidx.data_ptr(), jidx.numel(),
                  full.data_ptr(), 0 if full.dim() == 2 else full.shape[-2] * full.shape[-1], self._basis.n_ctrl,
                  self._basis.ic, self._basis.ec, _lib.ptr(st["params_init"]), _lib.ptr(st["params_end"]),
-                 _lib.ptr(st["init_pos"]),
+                 _lib.ptr(torch.zeros_like(st["init_pos"]) if order and st["init_pos"] is not None
+                          else st["init_pos"]),
                  _lib.stream_of(dev))
         return pos
 
@@ -841,6 +853,119 @@ class BEASTBsplineTokenizer(TokenizerBase):
             )
         params = params.to(torch.float32).contiguous()
         return self._reconstruct(None, params, times, kwargs.get("init_p"), False, p)
+
+    # ===============================================
+    #     - decoding to velocity / acceleration -
+    # ===============================================
+
+    @staticmethod
+    def _check_orders(orders) -> tuple:
+        try:
+            orders = tuple(orders)
+        except TypeError:
+            raise ValueError(f"orders must be a non-empty subset of (0, 1, 2); got {orders!r}") from None
+        if (not orders or len(set(orders)) != len(orders)
+                or any(isinstance(o, bool) or not isinstance(o, numbers.Integral) or o not in (0, 1, 2)
+                       for o in orders)):
+            raise ValueError(f"orders must be a non-empty subset of (0, 1, 2) without repeats; got {orders!r}")
+        return tuple(int(o) for o in orders)
+
+    def _deriv_basis_for(self, times, B: int, p: _Plan, orders: tuple):
+        """(order slabs [3][2][T][N] or per row [B][3][2][T][N], batch stride, T_out) for
+        beast_reconstruct_derivs_f32; the default grid's slabs are cached.  Only the requested
+        orders' slabs are evaluated (the kernel reads no other)."""
+        N, dev, kinds = self.num_basis, p.dev, self._basis.n_kinds
+        if times is None:
+            t = self.times.to(dev, dtype=torch.float32).reshape(-1)
+            return self._basis.deriv_constants(t, self._times_version), 0, p.T
+        t = times.to(dev, dtype=torch.float32)
+        if t.dim() == 2 and t.shape[0] == B and (B == 1 or torch.equal(t, t[:1].expand_as(t))):
+            t = t[0]
+        if t.dim() == 1:
+            Tn = t.numel()
+            slabs = torch.zeros((3, 2, Tn, N), dtype=torch.float32, device=dev)
+            for o in orders:
+                slabs[o, :kinds] = self._basis.deriv_basis_at(t, o)
+            return slabs, 0, Tn
+        if t.dim() != 2 or t.shape[0] != B:
+            raise ValueError(f"times must be [T] or [B, T]; got {tuple(t.shape)} for B={B}")
+        Tn = t.shape[1]
+        slabs = torch.zeros((B, 3, 2, Tn, N), dtype=torch.float32, device=dev)
+        for o in orders:
+            slabs[:, o, :kinds] = self._basis.deriv_basis_at(t, o).permute(1, 0, 2, 3)   # [kinds, B, T, N]
+        return slabs, 3 * 2 * Tn * N, Tn
+
+    def _reconstruct_derivs(self, tokens, ntokens, times, orders, init_p, respect_llm_vocab_size, p: _Plan):
+        orders = self._check_orders(orders)
+        src = tokens if tokens is not None else ntokens
+        B, D = src.shape[0], self.num_dof
+        slabs, basis_sb, Tn = self._deriv_basis_for(times, B, p, orders)
+        if Tn < 1:
+            raise ValueError("times must hold at least one point")
+        outs = [None, None, None]
+        for o in orders:
+            outs[o] = torch.empty((B, Tn, D), dtype=torch.float32, device=p.dev)
+        if B == 0:
+            return tuple(outs[o] for o in orders)
+        ip, ip_sb, ip_src = None, 0, None
+        if init_p is not None and self.init_pos and self.joint_dof > 0:
+            ip = torch.as_tensor(init_p).to(p.dev, dtype=torch.float32)
+            if ip.dim() != 2 or ip.shape[0] != B:
+                raise ValueError(f"init_p must be [B, num_dof]; got {tuple(ip.shape)}")
+            if ip.stride(1) != 1:
+                ip = ip.contiguous()
+            ip_sb, ip_src = ip.stride(0), p.p_dst      # joint DoFs come first in the dof map
+        offset = self._offset(respect_llm_vocab_size) if tokens is not None else 0
+        _lib.run("beast_reconstruct_derivs_f32", _lib.ptr(tokens), B, D, self.joint_dof, self.num_basis,
+                 self.vocab_size, offset, p.p_wmn, p.p_wmx, slabs.data_ptr(), basis_sb, Tn, p.p_dst, D,
+                 _lib.ptr(ip), ip_sb, ip_src, *map(_lib.ptr, outs), _lib.ptr(ntokens), _lib.raw_stream(p.idx))
+        if self._conditioned:
+            for o in orders:
+                outs[o] = self._add_conditions(outs[o], times, B, p.dev, order=o)
+        return tuple(outs[o] for o in orders)
+
+    def reconstruct_traj_derivs(self, tokens, times=None, orders=(0, 1, 2), *, init_p=None,
+                                respect_llm_vocab_size=True):
+        """Time derivatives of the decoded trajectory: a tuple of [B, T, num_dof] fp32 tensors, one
+        per entry of ``orders`` (any non-empty subset of (0, 1, 2) without repeats: position,
+        velocity, acceleration) in the order requested, from ONE launch of
+        ``beast_reconstruct_derivs_f32`` -- the tokens are read and dequantised once.
+
+        Order 1 is UniformBSpline.get_traj_vel (mp/uni_bspline.py:299-376); order 2 is the exact
+        second time derivative, not get_traj_acc's value.  Gripper DoFs (degree 0)
+        and any order above ``degree_p`` give zeros.  ``times`` is [T] or [B, T] as in
+        ``reconstruct_traj``; outside [0, duration] the boundary's one-sided derivative is returned.
+        With init / end conditions the last fit's conditions are used, as in ``reconstruct_traj``.
+
+        No autograd graph is recorded: the outputs are written by the kernel into fresh tensors."""
+        orders = self._check_orders(orders)
+        p = self._plan()
+        tokens = self._token_rows(tokens, p.dev)
+        return self._reconstruct_derivs(tokens, None, times, orders, init_p, respect_llm_vocab_size, p)
+
+    def reconstruct_traj_vel(self, tokens, times=None, **kwargs):
+        """Velocities [B, T, num_dof]: ``reconstruct_traj_derivs(..., orders=(1,))[0]``."""
+        return self.reconstruct_traj_derivs(tokens, times, (1,), **kwargs)[0]
+
+    def reconstruct_traj_acc(self, tokens, times=None, **kwargs):
+        """Accelerations [B, T, num_dof]: ``reconstruct_traj_derivs(..., orders=(2,))[0]``."""
+        return self.reconstruct_traj_derivs(tokens, times, (2,), **kwargs)[0]
+
+    @torch.no_grad()
+    def reconstruct_traj_continuous_derivs(self, params, times=None, orders=(0, 1, 2), **kwargs):
+        """``reconstruct_traj_derivs`` from normalised params in (t d) order (the
+        ``reconstruct_traj_continuous`` input); kwargs: init_p [B, num_dof]."""
+        orders = self._check_orders(orders)
+        p = self._plan()
+        params = params.to(p.dev)
+        if len(params.shape) == 3:
+            params = params.reshape(params.shape[0], -1)
+        if params.dim() != 2 or params.shape[-1] != self.num_basis * self.num_dof:
+            raise ValueError(
+                f"Token dimension {params.shape[-1]} does not match expected {self.num_basis * self.num_dof}."
+            )
+        params = params.to(torch.float32).contiguous()
+        return self._reconstruct_derivs(None, params, times, orders, kwargs.get("init_p"), False, p)
 
     # ===============================================
     #           - tokenizer evaluation -

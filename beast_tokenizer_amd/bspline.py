@@ -106,6 +106,57 @@ class DeviceBasis:
                      kv.numel(), self.degrees[k], self.num_basis, out[k].data_ptr(), s)
         return out
 
+    # ------------------------------------------------------------ derivatives --
+    def _deriv_into(self, t: torch.Tensor, kind: int, n_ctrl: int, order: int, out: torch.Tensor) -> None:
+        kv = self.knots(t.device, kind)
+        _lib.run("beast_bspline_basis_deriv_f32", t.data_ptr(), t.numel(), self.tau, self.delay, kv.data_ptr(),
+                 kv.numel(), self.degrees[kind], n_ctrl, order, out.data_ptr(), _lib.stream_of(t.device))
+
+    @staticmethod
+    def _check_order(order) -> int:
+        if isinstance(order, bool) or order not in (0, 1, 2):
+            raise ValueError(f"derivative order must be 0, 1 or 2; got {order!r}")
+        return int(order)
+
+    def full_deriv_basis_at(self, times: torch.Tensor, order: int) -> torch.Tensor:
+        """d^order/dt^order of the joint basis over all C control points, [*times.shape, C] fp32:
+        derivative = basis . control points (the reference differences the control points
+        instead, uni_bspline_basis.py:115-190).  Order 0 is ``full_basis_at`` bitwise."""
+        order = self._check_order(order)
+        _lib.require_gpu(times, "times")
+        t = times.to(torch.float32).contiguous()
+        out = torch.empty(tuple(t.shape) + (self.n_ctrl,), dtype=torch.float32, device=t.device)
+        self._deriv_into(t, 0, self.n_ctrl, order, out)
+        return out
+
+    def deriv_basis_at(self, times: torch.Tensor, order: int) -> torch.Tensor:
+        """``basis_at`` for the order-th time derivative -> [kinds, *times.shape, N] (kind 0: the
+        fitted columns, through the linear ``effective``; kind 1, degree 0: zeros for order >= 1)."""
+        order = self._check_order(order)
+        _lib.require_gpu(times, "times")
+        t = times.to(torch.float32).contiguous()
+        out = torch.empty((self.n_kinds,) + tuple(t.shape) + (self.num_basis,), dtype=torch.float32,
+                          device=t.device)
+        for k in range(self.n_kinds):
+            if k == 0 and self.conditioned:
+                out[0] = self.effective(self.full_deriv_basis_at(t, order))
+                continue
+            self._deriv_into(t, k, self.num_basis, order, out[k])
+        return out
+
+    def deriv_constants(self, times: torch.Tensor, version: int = 0) -> torch.Tensor:
+        """The order slabs [3][2][T][N] fp32 of beast_reconstruct_derivs_f32 for a 1-D grid, cached
+        per (device, version, T) as ``constants`` caches Phi."""
+        key = (times.device, "deriv", version, times.numel())
+        hit = self._cache.get(key)
+        if hit is None:
+            t = times.reshape(-1)
+            hit = torch.zeros((3, 2, t.numel(), self.num_basis), dtype=torch.float32, device=times.device)
+            for o in range(3):
+                hit[o, : self.n_kinds] = self.deriv_basis_at(t, o)
+            self._cache[key] = hit
+        return hit
+
     # ------------------------------------------------- boundary conditions --
     def knot_steps(self, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
         """(knots[1+p] - knots[1], knots[C-1+p] - knots[C-1]) fp32 (compute_init/end_params)."""

@@ -2,6 +2,8 @@
 //
 //   H1/H2  k_basis        Cox-de Boor basis at arbitrary times (bit-exact vs the
 //                         reference's fp32 recursion, uni_bspline_basis.py:82-113)
+//          k_basis_deriv  its first / second time derivative over the same control points
+//                         (replaces vel_basis + velocity_control_points, :115-190)
 //          k_projection   P = (Phi^T Phi + reg I)^-1 Phi^T in fp64 (one workgroup),
 //                         written zero-padded as [16][Tp] for the encode kernel
 //   H5     k_quantize     quantise-only epilogue (encode(update_bounds=True), continuous)
@@ -44,6 +46,43 @@ __global__ void k_basis(const float* __restrict__ times, int64_t n, float tau, f
   u = (u < 0.0f) ? 0.0f : u;
   u = (1.0f < u) ? 1.0f : u;
   for (int c = 0; c < nctrl; ++c) out[i * nctrl + c] = bfun<K>(c, u, kv, nctrl);
+}
+
+// d^R/du^R of B_{i,K} by the derivative rule applied R times (zero-denominator terms dropped as
+// bfun drops them): K * (dB_{i,K-1} / (k[i+K] - k[i]) - dB_{i+1,K-1} / (k[i+K+1] - k[i+1])).
+// R == 0 is bfun itself; R > K is identically zero.  The degree-0 spans keep bfun's rule
+// ([k_i, k_{i+1}), span nctrl - 1 closed), so a discontinuous derivative is right-continuous.
+template <int K, int R>
+__device__ float dbfun(int i, float u, const float* __restrict__ kv, int nctrl) {
+  if constexpr (R == 0) {
+    return bfun<K>(i, u, kv, nctrl);
+  } else if constexpr (K < R) {
+    return 0.0f;
+  } else {
+    const float d1 = __fsub_rn(kv[i + K], kv[i]);
+    const float d2 = __fsub_rn(kv[i + K + 1], kv[i + 1]);
+    float t1 = 0.0f, t2 = 0.0f;
+    if (!(d1 == 0.0f)) t1 = __fdiv_rn(dbfun<K - 1, R - 1>(i, u, kv, nctrl), d1);
+    if (!(d2 == 0.0f)) t2 = __fdiv_rn(dbfun<K - 1, R - 1>(i + 1, u, kv, nctrl), d2);
+    return __fmul_rn((float)K, __fsub_rn(t1, t2));
+  }
+}
+
+// k_basis for the R-th time derivative: one 1 / tau per order (u = (t - delay) / tau).
+template <int K, int R>
+__global__ void k_basis_deriv(const float* __restrict__ times, int64_t n, float tau, float delay,
+                              const float* __restrict__ kv, int nctrl, float* __restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float u = __fdiv_rn(__fsub_rn(times[i], delay), tau);
+  u = (u < 0.0f) ? 0.0f : u;
+  u = (1.0f < u) ? 1.0f : u;
+  for (int c = 0; c < nctrl; ++c) {
+    float v = dbfun<K, R>(c, u, kv, nctrl);
+#pragma unroll
+    for (int r = 0; r < R; ++r) v = __fdiv_rn(v, tau);
+    out[i * nctrl + c] = v;
+  }
 }
 
 // ------------------------------------------------------------- projection --
@@ -182,6 +221,43 @@ extern "C" int beast_bspline_basis_f32(const float* times, int64_t n_times, floa
   }
 #undef BEAST_BASIS_CASE
   BEAST_LAUNCHED("k_basis");
+  return BEAST_OK;
+}
+
+extern "C" int beast_bspline_basis_deriv_f32(const float* times, int64_t n_times, float tau, float delay,
+                                             const float* knots, int n_knots, int degree, int num_basis,
+                                             int order, float* basis_out, void* stream) {
+  BEAST_REQUIRE(times && knots && basis_out, "beast_bspline_basis_deriv_f32: null pointer");
+  BEAST_REQUIRE(order >= 0 && order <= 2, "beast_bspline_basis_deriv_f32: order must be 0, 1 or 2, got %d", order);
+  if (order == 0)   // the same kernel, so the same bits
+    return beast_bspline_basis_f32(times, n_times, tau, delay, knots, n_knots, degree, num_basis, basis_out, stream);
+  BEAST_REQUIRE(degree >= 0 && degree <= 8, "degree_p must be in [0, 8], got %d", degree);
+  BEAST_REQUIRE(num_basis >= 1 && n_knots == degree + 1 + num_basis, "knot vector size %d != degree+1+num_basis",
+                n_knots);
+  BEAST_REQUIRE(n_times >= 0, "beast_bspline_basis_deriv_f32: n_times=%lld must be >= 0", (long long)n_times);
+  if (n_times == 0) return BEAST_OK;
+  hipStream_t s = beast::as_stream(stream);
+  if (order > degree) {   // the spline's pieces have degree < order
+    BEAST_HIP(hipMemsetAsync(basis_out, 0, (size_t)n_times * num_basis * sizeof(float), s), "basis_deriv memset");
+    return BEAST_OK;
+  }
+  const int nthr = 256;
+  const int64_t nblk = (n_times + nthr - 1) / nthr;
+#define BEAST_DERIV_CASE(K)                                                                                      \
+  case K:                                                                                                        \
+    if (order == 1)                                                                                              \
+      hipLaunchKernelGGL((k_basis_deriv<K, 1>), dim3(nblk), dim3(nthr), 0, s, times, n_times, tau, delay, knots, \
+                         num_basis, basis_out);                                                                  \
+    else                                                                                                         \
+      hipLaunchKernelGGL((k_basis_deriv<K, 2>), dim3(nblk), dim3(nthr), 0, s, times, n_times, tau, delay, knots, \
+                         num_basis, basis_out);                                                                  \
+    break;
+  switch (degree) {
+    BEAST_DERIV_CASE(1) BEAST_DERIV_CASE(2) BEAST_DERIV_CASE(3) BEAST_DERIV_CASE(4)
+    BEAST_DERIV_CASE(5) BEAST_DERIV_CASE(6) BEAST_DERIV_CASE(7) BEAST_DERIV_CASE(8)
+  }
+#undef BEAST_DERIV_CASE
+  BEAST_LAUNCHED("k_basis_deriv");
   return BEAST_OK;
 }
 

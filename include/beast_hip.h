@@ -92,6 +92,24 @@ int beast_bspline_basis_f32(const float* times, int64_t n_times, float tau, floa
                             const float* knots, int n_knots, int degree, int num_basis,
                             float* basis_out, void* stream);
 
+/* The order-th TIME derivative of the same basis, over the SAME control points:
+ * basis_out[i][n] = d^order/dt^order B_{n,degree}(u) at u = clip((t_i - delay)/tau, 0, 1), so
+ * derivative = basis_out . params with no control-point differencing.  It stands in for
+ * UniBSplineBasis.vel_basis / acc_basis with velocity_control_points /
+ * acceleration_control_points (basis_gn/uni_bspline_basis.py:115-190), which
+ * UniformBSpline.get_traj_vel / get_traj_acc (mp/uni_bspline.py:299-459) combine:
+ *   D1[n] = (degree/tau) (B_{n,degree-1}(u)/(k[n+degree]-k[n]) - B_{n+1,degree-1}(u)/(k[n+degree+1]-k[n+1]))
+ * with zero-denominator terms dropped; order 2 applies the rule once more (span degree-1, a
+ * second 1/tau): the exact second derivative, NOT get_traj_acc's value, which is that times
+ * tau (degree-1)/degree on uniform knot spans.  order 0 runs beast_bspline_basis_f32's kernel (same
+ * bits); order in 0..2; order > degree gives zeros.  The phase is clipped first, so outside
+ * [delay, delay+tau] the boundary's one-sided derivative is returned; at an interior knot where
+ * the derivative jumps (order == degree) the value is the right-continuous one (spans
+ * [k_i, k_{i+1}), the last one closed: the reference's degree-0 rule). */
+int beast_bspline_basis_deriv_f32(const float* times, int64_t n_times, float tau, float delay,
+                                  const float* knots, int n_knots, int degree, int num_basis,
+                                  int order, float* basis_out, void* stream);
+
 /* Ridge projection P = (Phi^T Phi + reg I)^-1 Phi^T in float64: the closed form
  * of UniformBSpline.learn_mp_params_from_trajs (mp/uni_bspline.py:539-586) for
  * init/end condition order 0, where the block-diagonal system of
@@ -160,6 +178,29 @@ int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, int n_joint, 
                           const int32_t* dof_dst, int num_dof_out,
                           const float* init_p, int64_t init_p_sb, const int32_t* init_p_src,
                           float* params_out, float* pos_out, const float* ntokens, void* stream);
+
+/* Positions, velocities and accelerations from tokens in ONE launch: what
+ * UniformBSpline.get_traj_pos / get_traj_vel / get_traj_acc (mp/uni_bspline.py:114-177,
+ * :299-459) give for the decoded params, with the acceleration being the exact second time
+ * derivative (see beast_bspline_basis_deriv_f32).  Every argument means what it means in
+ * beast_reconstruct_f32 (token order (n d), tok_offset subtracted, ntokens, init_p, dof_dst,
+ * unnamed output columns written 0), except:
+ *   basis       [3][2][T_out][N] fp32, order-major: slab o holds the order-o basis of kind 0
+ *               (joint) and kind 1 (gripper); basis_sb = 0 (shared) or a per-trajectory stride
+ *               covering all three slabs.  The slab of a null output is never read (it may be
+ *               unallocated, as long as the used slabs sit at their order's offset).
+ *   pos_out, vel_out, acc_out   [B][T_out][num_dof_out] each; nullable, at least one given.
+ *               Gripper DoFs (d >= n_joint, degree 0) get 0 in vel_out and acc_out whatever
+ *               their slab holds.
+ * Tokens are read and dequantised once per trajectory; every requested order is written from
+ * that copy.  N <= 16, D <= 64, T_out <= 4096, num_dof_out <= 4096, else BEAST_E_UNSUPPORTED. */
+int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, int D, int n_joint, int N, int vocab,
+                                 int64_t tok_offset, const float* w_min, const float* w_max,
+                                 const float* basis, int64_t basis_sb, int T_out,
+                                 const int32_t* dof_dst, int num_dof_out,
+                                 const float* init_p, int64_t init_p_sb, const int32_t* init_p_src,
+                                 float* pos_out, float* vel_out, float* acc_out, const float* ntokens,
+                                 void* stream);
 
 /* ---------------------------------------------------- §8f rank 4: conditions ---
  * init_cond_order / end_cond_order != 0 (init_order in 0..2, end_order in -1..2, not both 0).
