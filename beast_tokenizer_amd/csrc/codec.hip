@@ -175,7 +175,7 @@ __device__ __forceinline__ void dma4(void* lds, const void* g, int n) {
 // library compiles them out): s_memtime of lane 0 of every wave of workgroup 0 at the
 // phase boundaries of its first tile.
 #ifdef BEAST_STAMPS
-__device__ unsigned long long g_stamps[2][8][16];
+__device__ unsigned long long g_stamps[2][16][16];   // [kernel][wave of a workgroup (<= 16)][stamp]
 #define STAMP(k, i)                                                                              \
   do {                                                                                           \
     if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) g_stamps[k][threadIdx.x >> 6][i] = __builtin_amdgcn_s_memtime(); \
@@ -570,20 +570,37 @@ __host__ __device__ constexpr EvSmem ev_smem(int nkinds) {
   s.whi = o;  o += round_up(PS::DN * 4, 256);
   s.lcol = o; o += round_up(PS::D * 4, 256);
   s.pimg = o; o += W * round_up(PS::DN * 4, 16);
-  s.timg = o; o += W * round_up(PS::DN * 8, 16);
+  s.timg = o; o += W * round_up(PS::DN * 8 + 8, 16);   // + one slot the padding lanes write to
   s.total = o;
   return s;
 }
 
+// Keeps a lane-only value that was computed before the tile barrier in its register: without it
+// the compiler sinks the arithmetic back behind the barrier, next to its use.
+template <class V>
+__device__ __forceinline__ void pin(V& v) {
+  asm volatile("" : "+v"(v));
+}
+
+// Round 7: the chain that runs after the tile barrier is shorter.  The quantiser runs three slots
+// per lane, not four: rows n = 4 lk + 3 of lanes lk < 2 move to slot 2 of lanes lk >= 2 (one
+// v_permlane32_swap), whose own rows there are padding (N <= 10), so 192 slots serve the 140 values.
+// The LDS addresses of a lane's operands, bounds and token-image slots depend on the lane alone and
+// are computed before the barrier, while the DMA is in flight; padding slots write to a spare image
+// slot instead of being predicated.  The bounds themselves still arrive by DMA: per-lane global
+// loads of them before the barrier cost more vector-memory issue time than the chain saves
+// (profiles/r07/codec_chain_ab.txt).
 template <class S, int SP, int W>
 __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ traj, int64_t B, EncVArgs a) {
   using PS = VShape<S>;
-  static_assert(PS::D <= 16 && PS::N <= 16 && PS::DL == PS::D, "per-trajectory encode: D, N <= 16, rows of D");
+  static_assert(PS::D <= 16 && PS::N <= 10 && PS::DL == PS::D,
+                "per-trajectory encode: D <= 16, rows of D, N <= 10 (three quantiser slots per lane)");
   constexpr int NT = W * 64, D = PS::D, N = PS::N, T = PS::T, Tp = PS::Tp, DN = PS::DN, NST = PS::NST;
   constexpr int NJ = S::NJ;
   constexpr int nkinds = NJ < D ? 2 : 1;
   constexpr EvSmem L = ev_smem<S, W>(nkinds);
-  constexpr int PIMG = round_up(DN * 4, 16) / 4, TIMG = round_up(DN * 8, 16) / 8;
+  constexpr int PIMG = round_up(DN * 4, 16) / 4, TIMG = round_up(DN * 8 + 8, 16) / 8;
+  constexpr int NQ = 3;   // quantiser slots per lane
   static_assert((T * D) % 4 == 0 && (DN % 2) == 0, "per-trajectory encode: whole 16-byte rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Y = reinterpret_cast<float*>(smem + L.Y);
@@ -607,27 +624,52 @@ __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ t
     dma4<NT>(whi, a.w_max, DN);
   }
   dma4<NT>(lcol, a.dof_src, D);
-  const float vm1 = (float)(a.vocab - 1);
-  __syncthreads();
-  STAMP(0, 2);
+  // ---- lane-only LDS addresses, computed while the DMA is in flight.  Lane (lr, lk): DoF d = lr;
+  //      slot u holds row n = 4 lk + u, slot 2 of lanes lk >= 2 row 4 (lk - 2) + 3
   const int j = wave;
-  if (j >= nb) return;   // no barrier follows
-  // ---- fit: lane (lr, lk): A = P_kind[n = lr][t = 4 st + lk], B = y[j][t][lcol[d = lr]] (t clamped
-  //      to T - 1: the zero-padded P columns meet those rows), even / odd steps accumulate apart
   const int lr = lane & 15, lk = lane >> 4;
   const bool dok = lr < D;
-  const int c = dok ? min(max(lcol[lr], 0), D - 1) : 0;
-  const float* yc = Y + j * T * D + c;
+  const float vm1 = (float)(a.vocab - 1);
+  int tq[NQ];   // byte offset of the slot's token in this wave's (n d) image
+  int kq[NQ];   // byte offset of the slot's (d n) column in a bounds array, clamped for the padding slots
+#pragma unroll
+  for (int u = 0; u < NQ; ++u) {
+    const int n = (u < 2 || lk < 2) ? 4 * lk + u : 4 * (lk - 2) + 3;
+    kq[u] = (min(lr, D - 1) * N + min(n, N - 1)) * 4;
+    tq[u] = L.timg + (j * TIMG + ((dok && n < N) ? n * D + lr : DN)) * 8;
+    pin(kq[u]); pin(tq[u]);
+  }
+  int yb = L.Y + (j * T * D + lk * D) * 4;
+  int yt = yb + (min(4 * (NST - 1) + lk, T - 1) - lk) * D * 4;   // the last K-step's row, clamped to T - 1
+  int pb = L.P + (lr * Tp + lk) * 4;
+  pin(yb); pin(yt); pin(pb);
+  __syncthreads();
+  STAMP(0, 2);
+  if (j >= nb) return;   // no barrier follows
+  // the DMA's clamped tail filled lcol[D ..] with the last DoF's column: no select for lanes lr >= D
+  const int c4 = min(max(lcol[lr], 0), D - 1) * 4;
+  yb += c4;
+  yt += c4;
+  float qlo[NQ] = {0.0f, 0.0f, 0.0f}, qhi[NQ] = {0.0f, 0.0f, 0.0f};
+  if (quant) {   // wave-uniform; read with the fit's operands
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      qlo[u] = *reinterpret_cast<const float*>(smem + L.wlo + kq[u]);
+      qhi[u] = *reinterpret_cast<const float*>(smem + L.whi + kq[u]);
+    }
+  }
+  // ---- fit: lane (lr, lk): A = P_kind[n = lr][t = 4 st + lk], B = y[j][t][lcol[d = lr]] (t clamped
+  //      to T - 1: the zero-padded P columns meet those rows), even / odd steps accumulate apart.
+  //      B columns d >= D are never stored, so with one kind they need no zeroing.
   float4_t acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = acc0;
 #pragma unroll
   for (int kd = 0; kd < nkinds; ++kd) {
-    const bool mine = dok && (nkinds == 1 || ((lr < NJ) == (kd == 0)));
-    const float* pa = P + (kd * 16 + lr) * Tp + lk;
+    const bool mine = nkinds == 1 || (dok && ((lr < NJ) == (kd == 0)));
     float xa[NST], ya[NST];
 #pragma unroll
     for (int st = 0; st < NST; ++st) {   // every operand read before the chain (one LDS round trip)
-      xa[st] = pa[4 * st];
-      const float y = yc[min(4 * st + lk, T - 1) * D];
+      xa[st] = *reinterpret_cast<const float*>(smem + pb + (kd * 16 * Tp + 4 * st) * 4);
+      const float y = *reinterpret_cast<const float*>(smem + (st + 1 < NST ? yb + 4 * st * D * 4 : yt));
       ya[st] = mine ? y : 0.0f;
     }
 #pragma unroll
@@ -641,7 +683,7 @@ __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ t
   //      into this wave's images; the quantiser is k_encode's (fast bins, the exact chain near a
   //      rounding boundary or for NaN / inf)
   float* pimg = reinterpret_cast<float*>(smem + L.pimg) + j * PIMG;
-  long long* timg = reinterpret_cast<long long*>(smem + L.timg) + j * TIMG;
+  const long long* timg = reinterpret_cast<const long long*>(smem + L.timg) + j * TIMG;
   float pv[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) pv[r] = __fadd_rn(acc0[r], acc1[r]);
@@ -654,27 +696,25 @@ __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ t
     }
   }
   if (quant) {
-    const unsigned long long off = (unsigned long long)a.tok_offset;
-    float lo[4], hi[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int k = lr * N + min(4 * lk + r, N - 1);
-      lo[r] = wlo[min(k, DN - 1)];
-      hi[r] = whi[min(k, DN - 1)];
-    }
-    int bin[4];
+    // slot 2: lanes lk < 2 keep their own row 4 lk + 2, lanes lk >= 2 take row 4 (lk - 2) + 3 of lane - 32
+    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(pv[2]), __float_as_uint(pv[3]), false, false);
+    const float qv[NQ] = {pv[0], pv[1], __uint_as_float(sw[0])};
+    int bin[NQ];
     bool ex = false;
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      bin[r] = beast::quantize_bin_k(pv[r], lo[r], hi[r], beast::quantize_scale(lo[r], hi[r], vm1), vm1, ex);
+    for (int u = 0; u < NQ; ++u)
+      bin[u] = beast::quantize_bin_k(qv[u], qlo[u], qhi[u], beast::quantize_scale(qlo[u], qhi[u], vm1), vm1, ex);
     if (ex) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) bin[r] = beast::quantize_bin(pv[r], lo[r], hi[r], vm1);
+      for (int u = 0; u < NQ; ++u) bin[u] = beast::quantize_bin(qv[u], qlo[u], qhi[u], vm1);
     }
-    if (dok) {
+    if (a.tok_offset == 0) {   // wave-uniform: no 64-bit add
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (4 * lk + r < N) timg[(4 * lk + r) * D + lr] = beast::widen_bin(bin[r], off);
+      for (int u = 0; u < NQ; ++u) *reinterpret_cast<long long*>(smem + tq[u]) = beast::widen_bin(bin[u], 0ull);
+    } else {
+      const unsigned long long off = (unsigned long long)a.tok_offset;
+#pragma unroll
+      for (int u = 0; u < NQ; ++u) *reinterpret_cast<long long*>(smem + tq[u]) = beast::widen_bin(bin[u], off);
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1072,9 +1112,23 @@ __global__ __launch_bounds__(S::W * 64) void k_reconstruct(const void* __restric
 // gripper DoFs the rows of the other kind are zero in each kind's chain: the joint chain then
 // the gripper chain, each adding exact zeros to the other kind's rows.
 
+// Round 7: the chain after the tile barrier is shorter.  Whatever depends on the lane alone is
+// computed before the barrier, while the DMA is in flight: the inverse DoF map (scalar loads of
+// a.dof_dst), and the LDS addresses of the lane's tokens, bounds, W-image slots and Phi^T operands.
+// Operands that must be zero (rows past T, K-steps past N, rows no DoF maps to) are read from a
+// zeroed LDS region instead of being selected, and slots past the trajectory's tokens write to a
+// spare W-image slot instead of being predicated.  After the barrier the three slots' tokens and
+// bounds are read in one LDS round trip, their LUT entries in a second, and tokens outside the LUT
+// take one IEEE-divide fallback behind the three fast paths.  Bounds and basis still arrive by DMA:
+// per-lane global loads of them cost more vector-memory issue time than the chain saves
+// (profiles/r07/codec_chain_ab.txt).
 struct RvSmem {
-  int tok, wlo, whi, dst, phi, lut, wimg, img, total;
+  int tok, wlo, whi, phi, zero, lut, wimg, img, total;
 };
+template <class S>
+__host__ __device__ constexpr int rv_zero_bytes(int nkinds) {   // every Phi^T operand offset, from a zero base
+  return round_up(((nkinds - 1) * S::T + round_up(S::T, 16)) * S::N * 4, 16);
+}
 template <class S>
 __host__ __device__ constexpr RvSmem rv_smem(int nkinds) {
   RvSmem s{};
@@ -1083,14 +1137,16 @@ __host__ __device__ constexpr RvSmem rv_smem(int nkinds) {
   s.tok = o;  o += round_up(RV_WR * per * 8, 1024);           // DMA: whole wave-instructions
   s.wlo = o;  o += round_up(per * 4, 256);
   s.whi = o;  o += round_up(per * 4, 256);
-  s.dst = o;  o += round_up(S::D * 4, 256);
   s.phi = o;  o += round_up(nkinds * S::T * S::N * 4, 1024);
+  s.zero = o; o += rv_zero_bytes<S>(nkinds);
   s.lut = o;  o += round_up(LUT_MAX * 4, 16);
-  s.wimg = o; o += round_up(RV_WR * per * 4, 16);              // W[j][d][n] (d n), one per wave
+  s.wimg = o; o += round_up(RV_WR * (per + 4) * 4, 16);        // W[j][d][n] (d n) + a spare slot, one per wave
   s.img = o;  o += RV_WR * round_up(S::T * S::D * 4, 16);        // pos[j] [T][D], one per wave
   s.total = o;
   return s;
 }
+
+typedef __attribute__((address_space(4))) const int32_t const_i32;   // constant memory: uniform reads are scalar loads
 
 template <int KS, class S, int SP>
 __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __restrict__ tsrc, int64_t B, int esz,
@@ -1102,24 +1158,24 @@ __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __rest
   constexpr int nkinds = NJ < D ? 2 : 1;
   constexpr RvSmem L = rv_smem<S>(nkinds);
   constexpr int RV_IMG = round_up(T * D * 4, 16) / 4;   // floats per wave's output image
+  constexpr int WIMG = per + 4;                         // floats per wave's W image; [per] is the spare slot
+  constexpr int NU = (per + 63) / 64;                   // dequantise slots per lane
+  constexpr int NTT = (T + 15) / 16;                    // 16-row tiles of the output
   static_assert((T * D) % 4 == 0, "per-trajectory reconstruct: whole 16-byte rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const unsigned char* tokl = smem + L.tok;
   float* wlo = reinterpret_cast<float*>(smem + L.wlo);
   float* whi = reinterpret_cast<float*>(smem + L.whi);
-  int* dst = reinterpret_cast<int*>(smem + L.dst);
   float* phi = reinterpret_cast<float*>(smem + L.phi);
   float* lut = reinterpret_cast<float*>(smem + L.lut);
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int64_t b0 = (int64_t)blockIdx.x * RV_WR;
   STAMP(1, 0);
   BSTAMP(1, 0);
-  // ---- prologue: the token tile, bounds, DoF map and raw basis by DMA, all in flight together
+  // ---- prologue: the token tile, bounds and raw basis by DMA, all in flight together
   stage_rows<NT>(smem + L.tok, tsrc, B, esz, b0, per, RV_WR);
   STAMP(1, 9);
   dma4<NT>(wlo, a.w_min, per);
   dma4<NT>(whi, a.w_max, per);
-  dma4<NT>(dst, a.dof_dst, D);
   {
     constexpr int pbytes = nkinds * T * N * 4;
     if ((pbytes & 15) == 0 && (((uintptr_t)a.basis) & 15) == 0) dma16<NT>(phi, a.basis, pbytes >> 4);
@@ -1127,70 +1183,116 @@ __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __rest
   }
   const float vm1 = (float)(a.vocab - 1);
   for (int t = tid; t < a.lut_n; t += NT) lut[t] = __fdiv_rn((float)t, vm1);
+  for (int i = tid; i < rv_zero_bytes<S>(nkinds) / 4; i += NT) reinterpret_cast<float*>(smem + L.zero)[i] = 0.0f;
   STAMP(1, 12);
-  __syncthreads();   // every DMA and the LUT are in place
-  STAMP(1, 2);
+  // ---- lane-only values, while the DMA is in flight
   const int j = wave;
   const int nb = (int)min<int64_t>(RV_WR, B - b0);
+  // dequantise slot u: token e = 64 u + lane of the trajectory, (n d) order -> W column k = d N + n
+  int te[NU], kb[NU], wk[NU];   // byte offsets: the token, its column in a bounds array, its W-image slot
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const int e = u * 64 + lane, ec = min(e, per - 1);
+    const int n = ec / D, d = ec - n * D, k = d * N + n;
+    te[u] = L.tok + (j * per + ec) * 8;
+    kb[u] = k * 4;
+    wk[u] = L.wimg + (j * WIMG + (e < per ? k : per)) * 4;
+    pin(te[u]); pin(kb[u]); pin(wk[u]);
+  }
+  // A = W: row c = lane & 15 is output column c, i.e. DoF d with dof_dst[d] == c; K-step s holds
+  // n = kk * KS + s (k_reconstruct's mapping), zero past N, past D and for the other kind
+  const int c = lane & 15, kk = lane >> 4;
+  int dsrc = -1;
+  const_i32* dof_dst = (const_i32*)a.dof_dst;
+#pragma unroll
+  for (int d = 0; d < D; ++d) dsrc = dof_dst[d] == c ? d : dsrc;
+  const bool row_ok = dsrc >= 0;
+  const int dd = row_ok ? dsrc : 0;
+  int wa[KS];            // byte offset of W[dd][n], or of a zero
+  unsigned am[nkinds];   // ~0 where the row belongs to the kind's chain
+#pragma unroll
+  for (int s2 = 0; s2 < KS; ++s2) {
+    const int n = kk * KS + s2;
+    wa[s2] = (row_ok && n < N) ? L.wimg + (j * WIMG + dd * N + n) * 4 : L.zero;
+    pin(wa[s2]);
+  }
+#pragma unroll
+  for (int kd = 0; kd < nkinds; ++kd) {
+    am[kd] = (nkinds == 1 || ((dd < NJ) == (kd == 0))) ? ~0u : 0u;
+    pin(am[kd]);
+  }
+  // B = Phi_kind^T: column t = 16 tt + c, K-step s: n = kk * KS + s.  pa: the whole row tiles
+  // (t < T for every c), pt: the last, partial one; kind and tile are constant offsets
+  int pa[KS], pt[KS];
+#pragma unroll
+  for (int s2 = 0; s2 < KS; ++s2) {
+    const int n = kk * KS + s2, tl = (NTT - 1) * 16 + c;
+    pa[s2] = n < N ? L.phi + (c * N + n) * 4 : L.zero;
+    pt[s2] = (n < N && tl < T) ? L.phi + (c * N + n) * 4 : L.zero;
+    pin(pa[s2]); pin(pt[s2]);
+  }
+  // this lane's part of pos[j]: row t = 16 tt + c, columns 4 kk .. 4 kk + 3
+  int ia = L.img + (j * RV_IMG + c * D + 4 * kk) * 4;
+  pin(ia);
+  __syncthreads();   // every DMA, the LUT and the zeros are in place
+  STAMP(1, 2);
   if (j >= nb) return;   // no barrier follows
   // ---- W[j][d][n] of this wave's trajectory (bit-exact discrete_to_continuous, init_p for n = 0 of
-  //      the joint DoFs: reference :505-510) into its LDS image
-  float* wimg = reinterpret_cast<float*>(smem + L.wimg) + j * per;
-  const long long* tk = reinterpret_cast<const long long*>(tokl) + j * per;
+  //      the joint DoFs: reference :505-510) into its LDS image: the slots' tokens and bounds in one
+  //      LDS round trip, their LUT entries in a second
+  long long tv[NU];
+  float lo[NU], hi[NU];
 #pragma unroll
-  for (int u = 0; u < (per + 63) / 64; ++u) {
-    const int e = u * 64 + lane;   // (n d) order
-    if (e < per) {
-      const int n = e / D, d = e - n * D, k = d * N + n;
-      const float lo = wlo[k], hi = whi[k];
-      const long long t = tk[e] - a.tok_offset;
-      const float nrm = (t >= 0 && t < a.lut_n) ? lut[(int)t] : __fdiv_rn((float)t, vm1);
-      float w = beast::clamp_t(__fadd_rn(__fmul_rn(nrm, __fsub_rn(hi, lo)), lo), lo, hi);
-      if (a.init_p != nullptr && n == 0 && d < NJ) w = a.init_p[(b0 + j) * a.init_p_sb + a.init_p_src[d]];
-      wimg[k] = w;
-    }
+  for (int u = 0; u < NU; ++u) {
+    tv[u] = *reinterpret_cast<const long long*>(smem + te[u]) - a.tok_offset;
+    lo[u] = *reinterpret_cast<const float*>(smem + L.wlo + kb[u]);
+    hi[u] = *reinterpret_cast<const float*>(smem + L.whi + kb[u]);
+  }
+  float nrm[NU];
+  bool far = false;
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const bool in = (unsigned long long)tv[u] < (unsigned long long)a.lut_n;   // 0 <= t < lut_n
+    far = far | !in;
+    nrm[u] = lut[in ? (int)tv[u] : 0];
+  }
+  if (far) {   // tokens outside the LUT (rare): the IEEE division
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if (!((unsigned long long)tv[u] < (unsigned long long)a.lut_n)) nrm[u] = __fdiv_rn((float)tv[u], vm1);
+  }
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    float w = beast::clamp_t(__fadd_rn(__fmul_rn(nrm[u], __fsub_rn(hi[u], lo[u])), lo[u]), lo[u], hi[u]);
+    if (u == 0 && a.init_p != nullptr && lane < NJ)   // slot 0 of lanes d < NJ is n = 0 of the joint DoFs
+      w = a.init_p[(b0 + j) * a.init_p_sb + a.init_p_src[lane]];
+    *reinterpret_cast<float*>(smem + wk[u]) = w;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   STAMP(1, 3);
-  // ---- A = W: row c = lane & 15 is output column c, i.e. DoF d with dst[d] == c; K-step s holds
-  //      n = kk * KS + s (k_reconstruct's mapping), zero past N, past D and for the other kind
-  const int c = lane & 15, kk = lane >> 4;
-  int dsrc = -1;
+  float4_t acc[NTT];
 #pragma unroll
-  for (int d = 0; d < D; ++d) dsrc = dst[d] == c ? d : dsrc;
-  const bool row_ok = dsrc >= 0;
-  const int dd = row_ok ? dsrc : 0;
-  float av[KS];
+  for (int tt = 0; tt < NTT; ++tt) acc[tt] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
+  float wv[KS];
 #pragma unroll
-  for (int s2 = 0; s2 < KS; ++s2) {
-    const int n = kk * KS + s2;
-    const float w = wimg[dd * N + min(n, N - 1)];
-    av[s2] = (row_ok && n < N) ? w : 0.0f;
-  }
-  // ---- B = Phi_kind^T: column t = 16 tt + (lane & 15), K-step s: n = kk * KS + s
-  float4_t acc[4];
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) acc[tt] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int s2 = 0; s2 < KS; ++s2) wv[s2] = *reinterpret_cast<const float*>(smem + wa[s2]);
 #pragma unroll
   for (int kd = 0; kd < nkinds; ++kd) {
-    float bv[4][KS];
+    float bv[NTT][KS];
 #pragma unroll
-    for (int tt = 0; tt < 4; ++tt)
+    for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
-      for (int s2 = 0; s2 < KS; ++s2) {
-        const int t = tt * 16 + c, n = kk * KS + s2;
-        const float x = phi[(kd * T + min(t, T - 1)) * N + min(n, N - 1)];
-        bv[tt][s2] = (t < T && n < N) ? x : 0.0f;
-      }
-    const bool mine = nkinds == 1 || ((dd < NJ) == (kd == 0));
+      for (int s2 = 0; s2 < KS; ++s2)
+        bv[tt][s2] = *reinterpret_cast<const float*>(smem + (tt * 16 + 15 < T ? pa[s2] : pt[s2]) +
+                                                     (kd * T + tt * 16) * N * 4);
 #pragma unroll
     for (int s2 = 0; s2 < KS; ++s2) {
-      const float ak = mine ? av[s2] : 0.0f;
+      const float ak = nkinds == 1 ? wv[s2] : __uint_as_float(__float_as_uint(wv[s2]) & am[kd]);
 #pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-        if (tt * 16 < T) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ak, bv[tt][s2], acc[tt], 0, 0, 0);
+      for (int tt = 0; tt < NTT; ++tt)
+        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ak, bv[tt][s2], acc[tt], 0, 0, 0);
     }
   }
   STAMP(1, 5);
@@ -1201,10 +1303,10 @@ __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __rest
   //      barrier) and copies it out as 16-byte write-through stores.
   float* img = reinterpret_cast<float*>(smem + L.img) + j * RV_IMG;
 #pragma unroll
-  for (int tt = 0; tt < 4; ++tt) {
+  for (int tt = 0; tt < NTT; ++tt) {
     const int t = tt * 16 + c;
-    if (tt * 16 < T && t < T) {
-      float* q = img + t * D + 4 * kk;
+    if (t < T) {
+      float* q = reinterpret_cast<float*>(smem + ia + tt * 16 * D * 4);
       if (4 * kk + 1 < D) *reinterpret_cast<float2*>(q) = make_float2(acc[tt][0], acc[tt][1]);
       else if (4 * kk < D) q[0] = acc[tt][0];
       if (4 * kk + 3 < D) *reinterpret_cast<float2*>(q + 2) = make_float2(acc[tt][2], acc[tt][3]);
@@ -1668,7 +1770,7 @@ extern "C" int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, in
 }
 
 #ifdef BEAST_STAMPS
-extern "C" int beast_stamps_read(unsigned long long* out) {   // [2][8][16]
+extern "C" int beast_stamps_read(unsigned long long* out) {   // [2][16][16]
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : -2;
 }
 

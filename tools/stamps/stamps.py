@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
 
-NW = 8   # stamp slots per kernel (waves per workgroup <= 8 in csrc/codec.hip)
+NW = 16   # stamp slots per kernel (waves per workgroup <= 16 in csrc/codec.hip: g_stamps[2][16][16])
 ENC = ["start", "issued", "landed", "mfma_done", "pb_ready", "params_stored", "tokens_stored", "drained", "acc_ready",
        "y_dma", "p_dma", "small_dma", "t2_landed", "t2_mfma_done", "t2_tokens_stored"]
 REC = ["start", "issued", "landed", "decoded", "w_ready", "mfma_done", "ob_ready", "stored", "drained",
@@ -66,7 +66,8 @@ def main():
     import torch
     from beast_tokenizer_amd import BEASTBsplineTokenizer, _lib
     from beast_tokenizer_amd.synthetic import synth_trajectories
-    so = os.path.join(HERE, "libbeast_stamps.so")   # built in the container (build()), travels along
+    # built in the container (build()), travels along; STAMPS_LIB names another -DBEAST_STAMPS build (A/B)
+    so = os.environ.get("STAMPS_LIB") or os.path.join(HERE, "libbeast_stamps.so")
     lib = C.CDLL(so if os.path.exists(so) and not os.environ.get("STAMPS_REBUILD") else build())
     for name, (res, args) in _lib.SIGNATURES.items():
         fn = getattr(lib, name)
