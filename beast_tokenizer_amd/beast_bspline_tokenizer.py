@@ -32,7 +32,7 @@ from __future__ import annotations
 import json
 import numbers
 from pathlib import Path
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -50,6 +50,29 @@ def _tqdm(it, **kw):
         return tqdm(it, **kw)
     except Exception:  # pragma: no cover
         return it
+
+
+class ReconstructionStats(NamedTuple):
+    """What ``reconstruction_stats`` returns: device tensors, one row per trajectory and one
+    column per output column (``[B, num_dof]`` fp32) unless noted."""
+    mse: torch.Tensor                    # mean_t (raw - reconstructed)^2
+    mean_err: torch.Tensor               # mean_t (raw - reconstructed), signed
+    max_abs: torch.Tensor                # max_t |raw - reconstructed| (NaN propagates)
+    mse_fit: Optional[torch.Tensor]      # mean_t (raw - spline fit)^2, before clamp / quantisation; None
+                                         #   for tokenizers with init / end conditions
+    clip_low: torch.Tensor               # int64 [num_dof, num_basis], w_min's (d n) order: trajectories
+    clip_high: torch.Tensor              #   whose param lies below w_min / above w_max
+    tokens: Optional[torch.Tensor]       # [B, num_basis*num_dof] as ``encode`` returns them, or None
+
+    @property
+    def l2(self) -> torch.Tensor:
+        """Batch mean of ``mse``: ``compute_reconstruction_error``'s first value."""
+        return self.mse.mean()
+
+    @property
+    def l1(self) -> torch.Tensor:
+        """Batch mean of ``mean_err``: ``compute_reconstruction_error``'s second value."""
+        return self.mean_err.mean()
 
 
 class _MPInfo:
@@ -970,6 +993,105 @@ class BEASTBsplineTokenizer(TokenizerBase):
     # ===============================================
     #           - tokenizer evaluation -
     # ===============================================
+
+    def _scatter_cols(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, D] in DoF order (joint ++ gripper) -> [B, num_dof] in output-column order."""
+        order = self.joint_indices + self.gripper_indices
+        if order == list(range(len(order))):
+            return x
+        out = torch.empty_like(x)
+        out[:, torch.as_tensor(order, device=x.device)] = x
+        return out
+
+    @torch.no_grad()
+    def reconstruction_stats(self, trajs, *, return_tokens=False, respect_llm_vocab_size=True):
+        """Per-trajectory, per-column error of encode -> reconstruct as a ``ReconstructionStats``,
+        from ONE launch of ``beast_roundtrip_stats_f32``: the trajectory is read once and neither
+        tokens, params nor positions travel through memory (the tokens only with
+        ``return_tokens``).  ``mse`` / ``mean_err`` / ``max_abs`` compare the input with exactly what
+        ``reconstruct_traj(encode(trajs)[0])`` returns; ``mse_fit`` is the same for the unquantised
+        spline fit, so ``mse - mse_fit`` is what clamping and quantisation add; ``clip_low`` /
+        ``clip_high`` count the trajectories whose params the bounds clamp.  ``.l2`` / ``.l1`` are
+        ``compute_reconstruction_error``'s two batch means.
+
+        ``trajs`` as for ``encode``: [B, T, >= num_dof] (or one [T, D] trajectory), any strides; other
+        dtypes are cast to fp32.  Tokenizers with init / end conditions take the composed path
+        (``encode`` + ``reconstruct_traj`` + torch reductions; ``encode`` stores the conditions as
+        usual) and return ``mse_fit = None``."""
+        p = self._plan()
+        trajs = torch.as_tensor(trajs)
+        if trajs.device != p.dev or trajs.dtype is not torch.float32:
+            trajs = trajs.to(p.dev, dtype=torch.float32)
+        if trajs.dim() == 2:
+            trajs = trajs.unsqueeze(0)
+        shape = trajs.shape
+        if len(shape) != 3 or shape[1] != p.T:
+            raise AssertionError(f"trajectory shape {tuple(shape)} does not match [B, {p.T}, num_dof] time grid")
+        B, T, Din = shape
+        if Din < p.min_din:
+            raise IndexError(f"index {p.min_din - 1} is out of bounds for dimension 2 with size {Din}")
+        D, N = self.num_dof, self.num_basis
+        offset = p.off if respect_llm_vocab_size else 0
+        if self._conditioned:
+            params, tokens = self._fit(trajs, offset, p)
+            pos = self._reconstruct(tokens, None, None, None, respect_llm_vocab_size, p)
+            err = trajs[..., :D] - pos
+            wmn, wmx = self._bounds(p.dev)
+            return ReconstructionStats((err * err).mean(dim=1), err.mean(dim=1), err.abs().amax(dim=1), None,
+                                       (params < wmn).sum(dim=0).reshape(D, N),
+                                       (params > wmx).sum(dim=0).reshape(D, N), tokens if return_tokens else None)
+        st = trajs.stride()
+        tokens = torch.empty((B, N * D), dtype=torch.int64, device=p.dev) if return_tokens else None
+        stats = torch.empty((B, D, 4), dtype=torch.float32, device=p.dev)
+        clip = torch.zeros((2, D * N), dtype=torch.int32, device=p.dev)   # the kernel's uint32 counters
+        _lib.run("beast_roundtrip_stats_f32", trajs.data_ptr(), B, T, st[0], st[1], st[2], Din, D, self.joint_dof,
+                 p.p_src, p.p_proj, p.p_phi, N, p.p_wmn, p.p_wmx, self.vocab_size, offset, _lib.ptr(tokens),
+                 stats.data_ptr(), clip.data_ptr(), _lib.raw_stream(p.idx))
+        inv_t = 1.0 / T
+        clip = clip.to(torch.int64).reshape(2, D, N)
+        return ReconstructionStats(self._scatter_cols(stats[..., 1] * inv_t), self._scatter_cols(stats[..., 0] * inv_t),
+                                   self._scatter_cols(stats[..., 2]), self._scatter_cols(stats[..., 3] * inv_t),
+                                   clip[0], clip[1], tokens)
+
+    @torch.no_grad()
+    def evaluate_reconstruction(self, dataloader, max_samples=None):
+        """``reconstruction_stats`` over a dataloader, accumulated on the device in float64 / int64
+        without a host synchronisation per batch.  Batches as for ``fit_parameters`` (a tensor, or
+        a dict with an ``"actions"`` entry; the last batch may be smaller); ``max_samples`` counts
+        batches, as it does there.  Returns a dict: ``mse``, ``mean_err``, ``max_abs``, ``mse_fit``
+        (float64 [num_dof], per output column: the means / the maximum over every trajectory seen;
+        ``mse_fit`` is None with init / end conditions), ``clip_low_rate``, ``clip_high_rate``
+        (float64 [num_dof, num_basis]: the share of trajectories whose param the bound clamps),
+        ``clip_low``, ``clip_high`` (the int64 counts) and ``num_samples`` (trajectories)."""
+        limit = max_samples if max_samples is not None else float("inf")
+        acc = None
+        count = batches = 0
+        for batch in dataloader:
+            if isinstance(batch, torch.Tensor):
+                actions = batch
+            else:
+                if "actions" not in batch:
+                    raise KeyError("Expected batch to contain an 'actions' entry.")
+                actions = batch["actions"]
+            r = self.reconstruction_stats(actions[..., : self.num_dof])
+            if r.mse.shape[0]:
+                cur = [r.mse.double().sum(dim=0), r.mean_err.double().sum(dim=0), r.max_abs.double().amax(dim=0),
+                       None if r.mse_fit is None else r.mse_fit.double().sum(dim=0), r.clip_low, r.clip_high]
+                if acc is None:
+                    acc = cur
+                else:
+                    acc = [None if a is None else (torch.maximum(a, c) if i == 2 else a + c)
+                           for i, (a, c) in enumerate(zip(acc, cur))]
+                count += r.mse.shape[0]
+            batches += 1
+            if batches >= limit:
+                break
+        if acc is None:
+            raise RuntimeError("No trajectories were gathered from the dataloader.")
+        return {"mse": acc[0] / count, "mean_err": acc[1] / count, "max_abs": acc[2],
+                "mse_fit": None if acc[3] is None else acc[3] / count,
+                "clip_low_rate": acc[4].double() / count, "clip_high_rate": acc[5].double() / count,
+                "clip_low": acc[4], "clip_high": acc[5], "num_samples": count}
 
     def compute_reconstruction_error(self, raw_traj, return_tokens=False):
         """(mean squared error, mean signed error) of encode -> reconstruct (reference :589-597)."""

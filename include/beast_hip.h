@@ -202,6 +202,32 @@ int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, int D, int n_
                                  float* pos_out, float* vel_out, float* acc_out, const float* ntokens,
                                  void* stream);
 
+/* Error statistics of encode -> reconstruct in ONE launch: how well the tokenizer represents the
+ * trajectories, and whether the spline fit or the quantiser is to blame.  traj .. dof_src, proj,
+ * N, w_min, w_max, vocab and tok_offset mean what they mean in beast_encode_f32; basis is
+ * beast_reconstruct_f32's shared grid [2][T][N] (basis_sb = 0, T_out = T).  With
+ * y[t] = traj[b][t][dof_src[d]], stats_out[b][d] (DoF order d = joint ++ gripper) holds
+ *   [0] sum_t e_t   [1] sum_t e_t^2   [2] max_t |e_t|   [3] sum_t f_t^2
+ * where e_t = y[t] - pos[t]: pos is, to the bit, what beast_reconstruct_f32 (no init_p) returns
+ * for the tokens beast_encode_f32 produces from this trajectory; and f_t = y[t] - fit[t]: fit is
+ * the same reconstruction of the unclamped, unquantised params (the bits of encode's
+ * params_out), i.e. the error of the spline fit alone.  The sums run in a fixed order (results
+ * are run-to-run identical); the maximum propagates NaN as torch.amax does, so a NaN sample makes
+ * all four values of its DoF NaN and leaves the other DoFs alone.
+ *   tokens_out   nullable [B][N*D]: exactly beast_encode_f32's tokens
+ *   stats_out    required [B][D][4] fp32
+ *   clip_counts  nullable uint32 [2][D*N] in (d n) order, ADDED to (the caller zero-fills):
+ *                [0] counts the trajectories whose param is < w_min, [1] those > w_max (NaN in
+ *                neither); one integer atomic per non-zero column and workgroup, so exact
+ * Same envelope as beast_encode_f32 (N <= 16, T <= 256, D <= 64, vocab >= 2, any strides and
+ * alignment); w_min and w_max are required.  The trajectory is read once (2,800 B at the default
+ * shape) and 16 B per (b, d) are written, plus the tokens if asked. */
+int beast_roundtrip_stats_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st, int64_t sd,
+                              int row_elems, int D, int n_joint, const int32_t* dof_src,
+                              const float* proj, const float* basis, int N,
+                              const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
+                              int64_t* tokens_out, float* stats_out, uint32_t* clip_counts, void* stream);
+
 /* ---------------------------------------------------- §8f rank 4: conditions ---
  * init_cond_order / end_cond_order != 0 (init_order in 0..2, end_order in -1..2, not both 0).
  * beast_cond_fixed_f32 replaces the per-fit condition step of UniBSpline.learn
