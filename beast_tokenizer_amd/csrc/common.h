@@ -55,17 +55,6 @@ __device__ __forceinline__ long long quantize_one(float p, float lo, float hi, f
   return (long long)r;
 }
 
-// quantize_one with the per-column scale s = clamp(hi - lo, min=1e-8) precomputed.
-__device__ __forceinline__ long long quantize_scaled(float p, float lo, float hi, float s, float vm1) {
-  const float x = clamp_t(p, lo, hi);
-  float u = __fdiv_rn(__fsub_rn(x, lo), s);
-  u = (u < 0.0f) ? 0.0f : u;
-  u = (1.0f < u) ? 1.0f : u;
-  const float r = rintf(__fmul_rn(u, vm1));
-  if (r != r) return (long long)0x8000000000000000ULL;
-  return (long long)r;
-}
-
 // quantize_one as a bin index: the same ops, int32 result, INT32_MIN for NaN (widened
 // to ATen's INT64_MIN by the caller).
 __device__ __forceinline__ int quantize_bin(float p, float lo, float hi, float vm1) {
@@ -79,25 +68,13 @@ __device__ __forceinline__ int quantize_bin(float p, float lo, float hi, float v
   return (r != r) ? (int)0x80000000 : (int)r;
 }
 
-// quantize_bin through a reciprocal: va = (x - lo) * (vm1 * rcp(s)) is within 3.6e-7 * vm1
-// of the exactly-rounded chain's u * vm1, so whenever va is farther than 2^-20 * vm1 from
-// a rounding boundary (k + 0.5) both round to the same bin; otherwise -- and for NaN /
-// inf -- the exact chain decides.  Bit-identical to quantize_bin for every input.
-__device__ __forceinline__ int quantize_bin_fast(float p, float lo, float hi, float vm1) {
-  const float x = clamp_t(p, lo, hi);
-  float s = __fsub_rn(hi, lo);
-  s = (s < 1e-8f) ? 1e-8f : s;
-  const float va = __fmul_rn(__fsub_rn(x, lo), __fmul_rn(vm1, __builtin_amdgcn_rcpf(s)));
-  const float f = __fsub_rn(va, floorf(va));
-  if (fabsf(__fsub_rn(f, 0.5f)) > 9.5367431640625e-7f * vm1) return (int)rintf(fminf(va, vm1));
-  return quantize_bin(p, lo, hi, vm1);
-}
-
-// quantize_bin_fast with the scale precomputed per (DoF, basis) column,
-// k = vm1 * rcp(max(hi - lo, 1e-8)) (NaN bounds give a NaN k): returns the fast bin and sets
-// `exact` when quantize_bin must decide instead (within 2^-20 * vm1 of a rounding boundary,
-// or a NaN / inf on the way).  med3 is clamp_t for lo <= hi; inverted bounds give va <= 0
-// -> bin 0, as the exact chain's clamp of u to [0, 1] does.
+// quantize_bin through a reciprocal, with the scale precomputed per (DoF, basis) column,
+// k = vm1 * rcp(max(hi - lo, 1e-8)) (NaN bounds give a NaN k): va = (x - lo) * k is within
+// 3.6e-7 * vm1 of the exactly-rounded chain's u * vm1, so whenever va is farther than 2^-20 * vm1
+// from a rounding boundary (j + 0.5) both round to the same bin.  Returns that fast bin and sets
+// `exact` when quantize_bin must decide instead (within 2^-20 * vm1 of a rounding boundary, or a
+// NaN / inf on the way).  med3 is clamp_t for lo <= hi; inverted bounds give va <= 0 -> bin 0, as
+// the exact chain's clamp of u to [0, 1] does.
 __device__ __forceinline__ int quantize_bin_k(float p, float lo, float hi, float k, float vm1, bool& exact) {
   const float x = __builtin_amdgcn_fmed3f(p, lo, hi);
   const float va = __fmul_rn(__fsub_rn(x, lo), k);
@@ -112,16 +89,33 @@ __device__ __forceinline__ float quantize_scale(float lo, float hi, float vm1) {
   return __fmul_rn(vm1, __builtin_amdgcn_rcpf(s));
 }
 
+// A lane's NQ slots: the fast bins with one shared `exact` flag, then the exact chain for all of
+// them where any slot asked for it.  Bit-identical to quantize_bin per slot.  k: the slots'
+// quantize_scale where the caller has them precomputed, else they are computed on the spot.
+template <int NQ>
+__device__ __forceinline__ void quantize_bins(const float (&p)[NQ], const float (&lo)[NQ], const float (&hi)[NQ],
+                                              float vm1, int (&bin)[NQ], const float* k = nullptr) {
+  bool ex = false;
+#pragma unroll
+  for (int u = 0; u < NQ; ++u)
+    bin[u] = quantize_bin_k(p[u], lo[u], hi[u], k ? k[u] : quantize_scale(lo[u], hi[u], vm1), vm1, ex);
+  if (ex) {
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) bin[u] = quantize_bin(p[u], lo[u], hi[u], vm1);
+  }
+}
+
 __device__ __forceinline__ long long widen_bin(int bin, unsigned long long offset) {
   const unsigned long long v = (bin == (int)0x80000000) ? 0x8000000000000000ULL : (unsigned long long)(long long)bin;
   return (long long)(v + offset);   // two's-complement wrap, as ATen's int64 add
 }
 
-// beast/utils.py:23-25, one element: int64 -> fp32, div, mul, add, clamp.
+// beast/utils.py:23-25, one element: int64 -> fp32, div, then (dequantize_quotient) mul, add, clamp.
+__device__ __forceinline__ float dequantize_quotient(float n, float lo, float hi) {
+  return clamp_t(__fadd_rn(__fmul_rn(n, __fsub_rn(hi, lo)), lo), lo, hi);
+}
 __device__ __forceinline__ float dequantize_one(long long tok, float lo, float hi, float vm1) {
-  float n = __fdiv_rn((float)tok, vm1);
-  float c = __fadd_rn(__fmul_rn(n, __fsub_rn(hi, lo)), lo);
-  return clamp_t(c, lo, hi);
+  return dequantize_quotient(__fdiv_rn((float)tok, vm1), lo, hi);
 }
 
 // beast/utils.py:29-35 normalize_tensor, one element (norm range [-1, 1]).

@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -221,43 +222,32 @@ __global__ __launch_bounds__(DV_THREADS) void k_reconstruct_derivs(DerivArgs a) 
   }
 }
 
-int dv_cu_count() {
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) == hipSuccess &&
-      hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-    return v;
-  return 256;
-}
-
 // LDS: W [TB][D][NP] | staged slabs | w_min, w_max [D*N] | col2d [num_dof_out]
 template <int KS, bool LB, int TB>
-int launch_derivs(DerivArgs a, int phi_bytes, int cus, hipStream_t s) {
+int launch_derivs(DerivArgs a, int phi_bytes, int cus, const Queue& q) {
   a.ntiles = (a.B + TB - 1) / TB;
   a.off_phi = TB * a.D * 4 * KS * 4;
   a.off_wlo = a.off_phi + (LB ? phi_bytes : 0);
   a.off_col = a.off_wlo + 2 * a.N * a.D * 4;
   const int lds = a.off_col + a.ndo * 4;
   BEAST_REQUIRE_CODE(lds <= 160 * 1024, BEAST_E_UNSUPPORTED, "reconstruct derivs tile needs %d B of LDS", lds);
-  const void* fn = reinterpret_cast<const void*>(&k_reconstruct_derivs<KS, LB, TB>);
-  if (lds > 65536)
-    BEAST_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds),
-              "hipFuncSetAttribute(k_reconstruct_derivs)");
-  // resident workgroups only: each stages the slabs once and strides over the tiles
+  // resident workgroups only: each stages the slabs once and strides over the tiles (half of
+  // grid_for's cap, which lets a second round of workgroups queue up)
   const int per_cu = std::max(1, std::min(8, (160 * 1024) / std::max(lds, 1)));
   const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(a.ntiles, (int64_t)cus * per_cu));
-  hipLaunchKernelGGL((k_reconstruct_derivs<KS, LB, TB>), dim3((unsigned)grid), dim3(DV_THREADS), lds, s, a);
-  BEAST_LAUNCHED("k_reconstruct_derivs");
-  return BEAST_OK;
+  static FnCache fn = {};
+  return launch_fn(reinterpret_cast<const void*>(&k_reconstruct_derivs<KS, LB, TB>), fn, (unsigned)grid, DV_THREADS,
+                   lds, q, "k_reconstruct_derivs", a);
 }
 
 template <int KS>
-int launch_derivs_ks(const DerivArgs& a, bool lb, int phi_bytes, hipStream_t s) {
-  const int cus = dv_cu_count();
+int launch_derivs_ks(const DerivArgs& a, bool lb, int phi_bytes, const Queue& q) {
+  const int cus = cu_count(q.dev);
   if ((a.B + DV_TILE - 1) / DV_TILE < 2 * (int64_t)cus)   // latency regime: more, smaller tiles
-    return lb ? launch_derivs<KS, true, DV_TILE_SMALL>(a, phi_bytes, cus, s)
-              : launch_derivs<KS, false, DV_TILE_SMALL>(a, phi_bytes, cus, s);
-  return lb ? launch_derivs<KS, true, DV_TILE>(a, phi_bytes, cus, s)
-            : launch_derivs<KS, false, DV_TILE>(a, phi_bytes, cus, s);
+    return lb ? launch_derivs<KS, true, DV_TILE_SMALL>(a, phi_bytes, cus, q)
+              : launch_derivs<KS, false, DV_TILE_SMALL>(a, phi_bytes, cus, q);
+  return lb ? launch_derivs<KS, true, DV_TILE>(a, phi_bytes, cus, q)
+            : launch_derivs<KS, false, DV_TILE>(a, phi_bytes, cus, q);
 }
 
 }  // namespace
@@ -302,11 +292,12 @@ extern "C" int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, in
     if (a.out[o]) phi_floats += ((o == 0 && n_joint < D) ? 2 : 1) * T_out * NP;
   }
   const bool lb = basis_sb == 0 && (int64_t)phi_floats * 4 <= DV_BASIS_LDS;
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  if (const int rc = queue_of(stream, q, "beast_reconstruct_derivs_f32")) return rc;
   switch (KS) {
-    case 1: return launch_derivs_ks<1>(a, lb, phi_floats * 4, s);
-    case 2: return launch_derivs_ks<2>(a, lb, phi_floats * 4, s);
-    case 3: return launch_derivs_ks<3>(a, lb, phi_floats * 4, s);
-    default: return launch_derivs_ks<4>(a, lb, phi_floats * 4, s);
+    case 1: return launch_derivs_ks<1>(a, lb, phi_floats * 4, q);
+    case 2: return launch_derivs_ks<2>(a, lb, phi_floats * 4, q);
+    case 3: return launch_derivs_ks<3>(a, lb, phi_floats * 4, q);
+    default: return launch_derivs_ks<4>(a, lb, phi_floats * 4, q);
   }
 }

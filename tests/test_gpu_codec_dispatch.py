@@ -1,6 +1,7 @@
 """Every encode / reconstruct launch branch of csrc/codec.hip against the float64 oracle.
 
-``launch_encode`` / ``launch_reconstruct`` choose among about twenty kernel instantiations by batch
+``launch_encode`` / ``launch_reconstruct`` (csrc/codec.hip; the kernels themselves are in
+csrc/codec_encode.h and csrc/codec_reconstruct.h, the launch path in csrc/launch.h) choose among about twenty kernel instantiations by batch
 size against the CU count, contiguity, 16-byte alignment of inputs and outputs, T * row_elems, N,
 T_out, the LDS footprint and whether the basis is shared.  Each row of the two tables below names a
 shape, the way to reach one branch and the fields of ``BEAST_OPT_LAST_CODEC_LAUNCH`` that branch

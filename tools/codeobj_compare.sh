@@ -3,7 +3,10 @@
 # worktree with the library's own flags and compares, per translation unit, the gfx950 code
 # object's .text and .rodata (kernel code + descriptors) with the current in-tree build
 # (beast_tokenizer_amd/csrc/build).  The host wrappers and the fat binary's bundle metadata
-# (which carries paths) are not compared.      bash tools/codeobj_compare.sh REV
+# (which carries paths) are not compared.  A unit that differs is disassembled on both sides and
+# listed per kernel symbol: same / DIFFERENT by instruction text alone (addresses, encodings and
+# branch targets stripped), with the VGPR / SGPR / LDS / scratch of both builds beside a kernel
+# that differs.                                bash tools/codeobj_compare.sh REV
 set -eu
 REV="$1"; R="$(cd "$(dirname "$0")/.." && pwd)"; W=/tmp/codeobj_wt_$$; O=/tmp/codeobj_o_$$
 B=/opt/rocm/lib/llvm/bin
@@ -30,5 +33,49 @@ for o in "$O"/*.o; do
   done
   if [ -z "$r" ]; then for s in .text .rodata; do cmp -s "$O/old$s" "$O/new$s" && r="$r $s same" || r="$r $s DIFFERENT"; done; fi
   echo "$f:$r"
+  case "$r" in *DIFFERENT*) python3 - "$B" "$O/old.co" "$O/new.co" <<'PY'
+import re, subprocess, sys
+B, old, new = sys.argv[1:4]
+
+
+def kernels(co):
+    """symbol -> its instructions as text: no addresses, no encodings, no branch targets"""
+    out, cur = {}, None
+    dis = subprocess.run([B + "/llvm-objdump", "-d", co], capture_output=True, text=True, check=True).stdout
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and line.startswith("\t"):
+            ins = line.split("//")[0].strip()
+            cur.append(ins.split()[0] if re.match(r"s_c?branch", ins) else ins)
+    return out
+
+
+def resources(co):
+    """kernel symbol -> the descriptor fields that matter, from the code object's metadata note"""
+    note = subprocess.run([B + "/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+    res = {}
+    for blk in re.split(r"\n\s+- \.agpr_count:", note)[1:]:
+        f = dict(re.findall(r"\.(name|vgpr_count|sgpr_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\S+)",
+                            blk))
+        res[f.get("name")] = "vgpr %s sgpr %s lds %s scratch %s" % (
+            f.get("vgpr_count"), f.get("sgpr_count"), f.get("group_segment_fixed_size"),
+            f.get("private_segment_fixed_size"))
+    return res
+
+
+ko, kn, ro, rn = kernels(old), kernels(new), resources(old), resources(new)
+names = sorted(set(ko) | set(kn))
+for k in names:
+    if k not in ko or k not in kn:
+        print("    %s: only in the %s build" % (k, "new" if k in kn else "old"))
+    elif ko[k] == kn[k]:
+        print("    %s: same" % k)
+    else:
+        print("    %s: DIFFERENT (%d -> %d instructions; old %s; new %s)" % (k, len(ko[k]), len(kn[k]), ro.get(k), rn.get(k)))
+print("    %d of %d kernels same" % (sum(1 for k in names if ko.get(k) == kn.get(k)), len(names)))
+PY
+  ;; esac
 done
 git -C "$R" worktree remove --force "$W"; rm -rf "$O"

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
 
-NW = 16   # stamp slots per kernel (waves per workgroup <= 16 in csrc/codec.hip: g_stamps[2][16][16])
+NW = 16   # stamp slots per kernel (waves per workgroup <= 16; g_stamps[2][16][16] in csrc/codec_device.h, part of codec.hip)
 ENC = ["start", "issued", "landed", "mfma_done", "pb_ready", "params_stored", "tokens_stored", "drained", "acc_ready",
        "y_dma", "p_dma", "small_dma", "t2_landed", "t2_mfma_done", "t2_tokens_stored"]
 REC = ["start", "issued", "landed", "decoded", "w_ready", "mfma_done", "ob_ready", "stored", "drained",
