@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "launch.h"
 #include "pretok.h"
 
 namespace {
@@ -1454,18 +1455,13 @@ inline int log2_ceil(int64_t x) {
   return l;
 }
 
-// rows -> workgroups: at most the ones resident at once (per_cu from the occupancy of the launch:
-// each workgroup stages the merge map once and then loops over rows)
-int grid_for(int64_t n_rows, int per_cu = 4) {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  const int64_t want = (n_rows + WAVES - 1) / WAVES;
-  const int64_t cap = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
-  return (int)(want < cap ? want : cap);
+// k_bpe_encode, nwv rows (waves) per workgroup: at most the workgroups resident at once (each
+// stages the merge map once and then loops over rows)
+template <bool MAP, int RM>
+int launch_bpe_encode(const EncArgs& a, int nwv, unsigned lds, const Queue& q) {
+  const int per_cu = std::max(1, occupancy<k_bpe_encode<MAP, RM>>(64 * nwv, lds, q));
+  const int64_t grid = std::min<int64_t>((a.n_rows + nwv - 1) / nwv, (int64_t)cu_count(q.dev) * per_cu);
+  return launch<k_bpe_encode<MAP, RM>>((unsigned)grid, 64 * nwv, lds, q, "k_bpe_encode", a);
 }
 
 }  // namespace
@@ -1511,13 +1507,13 @@ extern "C" int beast_bpe_mergemap_build(const int32_t* merge_a, const int32_t* m
   BEAST_REQUIRE(n_merges == 0 || (merge_a && merge_b && merge_new), "merge arrays are null");
   const MergeMap m = map_view(map, n_merges);
   const int cap = 1 << m.log2cap;
-  hipStream_t s = beast::as_stream(stream);
-  hipLaunchKernelGGL(k_mergemap_clear, dim3((cap + 255) / 256), dim3(256), 0, s, const_cast<uint2*>(m.kv), cap);
-  BEAST_LAUNCHED("k_mergemap_clear");
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_mergemap_build"));
+  BEAST_TRY(launch<k_mergemap_clear>((cap + 255) / 256, 256, 0, q, "k_mergemap_clear", const_cast<uint2*>(m.kv), cap));
   if (n_merges > 0) {
-    hipLaunchKernelGGL(k_mergemap_build, dim3((n_merges + 255) / 256), dim3(256), 0, s, merge_a, merge_b, merge_new,
-                       n_merges, const_cast<uint2*>(m.kv), const_cast<uint16_t*>(m.rank2new), m.log2cap);
-    BEAST_LAUNCHED("k_mergemap_build");
+    BEAST_TRY(launch<k_mergemap_build>((n_merges + 255) / 256, 256, 0, q, "k_mergemap_build", merge_a, merge_b,
+                                       merge_new, n_merges, const_cast<uint2*>(m.kv), const_cast<uint16_t*>(m.rank2new),
+                                       m.log2cap));
   }
   return BEAST_OK;
 }
@@ -1568,26 +1564,11 @@ extern "C" int beast_bpe_encode_rows(const int64_t* tok, const int64_t* row_off,
   a.out_ids = out_ids; a.out_stride = out_stride; a.out_len = out_len; a.status = status;
   const size_t lds = rows_lds + (a.map_in_lds ? map_lds : 0);
   const bool narrow = max_row_syms <= 64 * RM_NARROW;   // every row fits the narrow kernel's round merge
-  const void* fn = a.map_in_lds ? (narrow ? reinterpret_cast<const void*>(&k_bpe_encode<true, RM_NARROW>)
-                                          : reinterpret_cast<const void*>(&k_bpe_encode<true, RM_PER>))
-                                : (narrow ? reinterpret_cast<const void*>(&k_bpe_encode<false, RM_NARROW>)
-                                          : reinterpret_cast<const void*>(&k_bpe_encode<false, RM_PER>));
-  if (lds > 65536)
-    BEAST_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-              "hipFuncSetAttribute(k_bpe_encode)");
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * nwv, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
-  const int grid = (int)std::min<int64_t>((n_rows + nwv - 1) / nwv, (int64_t)grid_for(1 << 30, per_cu));
-  if (a.map_in_lds && narrow)
-    hipLaunchKernelGGL((k_bpe_encode<true, RM_NARROW>), dim3(grid), dim3(64 * nwv), lds, beast::as_stream(stream), a);
-  else if (a.map_in_lds)
-    hipLaunchKernelGGL((k_bpe_encode<true, RM_PER>), dim3(grid), dim3(64 * nwv), lds, beast::as_stream(stream), a);
-  else if (narrow)
-    hipLaunchKernelGGL((k_bpe_encode<false, RM_NARROW>), dim3(grid), dim3(64 * nwv), lds, beast::as_stream(stream), a);
-  else
-    hipLaunchKernelGGL((k_bpe_encode<false, RM_PER>), dim3(grid), dim3(64 * nwv), lds, beast::as_stream(stream), a);
-  BEAST_LAUNCHED("k_bpe_encode");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_encode_rows"));
+  if (a.map_in_lds)
+    return narrow ? launch_bpe_encode<true, RM_NARROW>(a, nwv, lds, q) : launch_bpe_encode<true, RM_PER>(a, nwv, lds, q);
+  return narrow ? launch_bpe_encode<false, RM_NARROW>(a, nwv, lds, q) : launch_bpe_encode<false, RM_PER>(a, nwv, lds, q);
 }
 
 
@@ -1680,21 +1661,11 @@ extern "C" int beast_bpe_encode_rows_words(const int64_t* tok, const int64_t* ro
   const int ltab_log2 = dw_ltab_log2(a.Lc, nwv);
   const int hash_shift = 32 - std::min(32, std::max(1, beast::g_bpe_dedup_key_bits));
   const size_t lds = bw_lds_bytes(a.Lc, a.S, nwv, map_log2);
-  hipStream_t s = beast::as_stream(stream);
-  const dim3 grid((unsigned)((n_rows + nwv - 1) / nwv)), block(64 * nwv);
-  if (map_log2 >= 0) {
-    if (lds > 65536)
-      BEAST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bpe_words<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(k_bpe_words)");
-    hipLaunchKernelGGL(k_bpe_words<true>, grid, block, lds, s, a, wm, ltab_log2, hash_shift);
-  } else {
-    if (lds > 65536)
-      BEAST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bpe_words<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(k_bpe_words)");
-    hipLaunchKernelGGL(k_bpe_words<false>, grid, block, lds, s, a, wm, ltab_log2, hash_shift);
-  }
-  BEAST_LAUNCHED("k_bpe_words");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_encode_rows_words"));
+  const unsigned grid = (unsigned)((n_rows + nwv - 1) / nwv), block = 64 * nwv;
+  return map_log2 >= 0 ? launch<k_bpe_words<true>>(grid, block, lds, q, "k_bpe_words", a, wm, ltab_log2, hash_shift)
+                       : launch<k_bpe_words<false>>(grid, block, lds, q, "k_bpe_words", a, wm, ltab_log2, hash_shift);
 }
 
 extern "C" int beast_bpe_decode_rows(const int32_t* ids, const int64_t* row_off, int64_t n_rows,
@@ -1714,8 +1685,8 @@ extern "C" int beast_bpe_decode_rows(const int32_t* ids, const int64_t* row_off,
   if (bcap > (int64_t)(LDS_BUDGET / WAVES)) bcap = LDS_BUDGET / WAVES;
   a.bcap = (int)bcap;
   a.out = reinterpret_cast<long long*>(out); a.out_count = out_count; a.status = status;
-  hipLaunchKernelGGL(k_bpe_decode, dim3(grid_for(n_rows)), dim3(BLOCK), (size_t)WAVES * al16(a.bcap),
-                     beast::as_stream(stream), a);
-  BEAST_LAUNCHED("k_bpe_decode");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_decode_rows"));
+  const int64_t grid = std::min<int64_t>((n_rows + WAVES - 1) / WAVES, 4 * (int64_t)cu_count(q.dev));
+  return launch<k_bpe_decode>((unsigned)grid, BLOCK, WAVES * al16(a.bcap), q, "k_bpe_decode", a);
 }

@@ -49,7 +49,7 @@ __device__ __forceinline__ unsigned long long sig_of(Get s, uint32_t L) {
 }
 
 // workgroups for n items at per_block items each, at least 1 and at most cap
-static inline int grid_for(int64_t n, int per_block, int cap) {
+static inline int blocks_for(int64_t n, int per_block, int cap) {
   const int64_t g = (n + per_block - 1) / per_block;
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
 }

@@ -16,6 +16,7 @@
 
 #include "bpe_common.h"
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -1412,16 +1413,20 @@ __global__ void k_loop_init(LoopState* st, LoopState init, LoopHash lh, int n_to
 }
 
 // k_merge's grid: the workgroups the device holds at once (one pass over the words, each
-// workgroup its chunks round-robin, MERGE_SCAN signature loads in flight per thread), not more
-template <class K>
-int resident_grid(K kernel, int threads, size_t lds, int per_default) {
-  int dev = 0, cus = 0, per = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, lds) != hipSuccess || per <= 0)
-    per = per_default;
-  return cus * per;
+// workgroup its chunks round-robin, MERGE_SCAN signature loads in flight per thread), not more.
+// Of the stream's device, and cached per kernel and device as cu_count is: the host-driven merge
+// loop asks once per merge.
+template <auto K>
+int resident_grid(int threads, unsigned lds, int per_default, const Queue& q) {
+  static std::atomic<int> n[16] = {};
+  const bool cached = q.dev >= 0 && q.dev < 16;
+  int v = cached ? n[q.dev].load(std::memory_order_relaxed) : 0;
+  if (v == 0) {
+    const int per = occupancy<K>(threads, lds, q);
+    v = cu_count(q.dev) * (per > 0 ? per : per_default);
+    if (cached) n[q.dev].store(v, std::memory_order_relaxed);
+  }
+  return v;
 }
 
 }  // namespace
@@ -1432,11 +1437,11 @@ extern "C" size_t beast_bpe_argmax_workspace_bytes(int Vt) { return (size_t)(4 +
 extern "C" int beast_bpe_argmax(const uint32_t* table, int Vt, int vcur, uint64_t* ws, int call, void* stream) {
   BEAST_REQUIRE(table && ws && vcur >= 1 && vcur <= Vt, "beast_bpe_argmax: bad args");
   BEAST_REQUIRE(call >= 0, "beast_bpe_argmax: call index must be >= 0");
-  hipLaunchKernelGGL(k_apply_argmax, dim3((vcur + APPLY_ROWS - 1) / APPLY_ROWS), dim3(64 * APPLY_ROWS), 0,
-                     beast::as_stream(stream), const_cast<uint32_t*>(table), nullptr, Vt, vcur, argws_view(ws, Vt),
-                     call & 1, 0, 0, 0, 0, nullptr, vcur);
-  BEAST_LAUNCHED("k_apply_argmax");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_argmax"));
+  return launch<k_apply_argmax>((vcur + APPLY_ROWS - 1) / APPLY_ROWS, 64 * APPLY_ROWS, 0, q, "k_apply_argmax",
+                                const_cast<uint32_t*>(table), nullptr, Vt, vcur, argws_view(ws, Vt), call & 1, 0, 0, 0,
+                                0, nullptr, vcur);
 }
 
 extern "C" int beast_bpe_apply_argmax(uint32_t* table, int32_t* deltas, int Vt, int vcur, int a, int b, int new_id,
@@ -1447,11 +1452,10 @@ extern "C" int beast_bpe_apply_argmax(uint32_t* table, int32_t* deltas, int Vt, 
                 "beast_bpe_apply_argmax: ids out of range");
   // every row that can change must run: rows < vcur, and a / b / new_id
   const int rows = std::max(vcur, std::max(a, std::max(b, new_id)) + 1);
-  hipLaunchKernelGGL(k_apply_argmax, dim3((rows + APPLY_ROWS - 1) / APPLY_ROWS), dim3(64 * APPLY_ROWS), 0,
-                     beast::as_stream(stream), table, deltas, Vt, vcur, argws_view(ws, Vt), call & 1, 1, a, b, new_id,
-                     tlen, rows);
-  BEAST_LAUNCHED("k_apply_argmax");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_apply_argmax"));
+  return launch<k_apply_argmax>((rows + APPLY_ROWS - 1) / APPLY_ROWS, 64 * APPLY_ROWS, 0, q, "k_apply_argmax", table,
+                                deltas, Vt, vcur, argws_view(ws, Vt), call & 1, 1, a, b, new_id, tlen, rows);
 }
 
 extern "C" int beast_bpe_merge(uint16_t* sym, const uint32_t* wstart, uint32_t* wlen, const uint32_t* wcount,
@@ -1461,22 +1465,18 @@ extern "C" int beast_bpe_merge(uint16_t* sym, const uint32_t* wstart, uint32_t* 
   BEAST_REQUIRE(a >= 0 && a < Vt && b >= 0 && b < Vt && new_id >= 0 && new_id < Vt && Vt <= 65535,
                 "beast_bpe_merge: ids out of range (a=%d b=%d new=%d Vt=%d)", a, b, new_id, Vt);
   if (n_words <= 0) return BEAST_OK;
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_merge"));
   const size_t lds = (size_t)4 * Vt * sizeof(int32_t);
   const bool use_lds = lds <= 64 * 1024 && pair_count >= beast::g_merge_lds_min;
-  static int resident[2] = {0, 0};
-  int& r = resident[use_lds];
-  if (r == 0) r = use_lds ? resident_grid(k_merge<true>, 256, 64 * 1024, 2) : resident_grid(k_merge<false>, 256, 0, 4);
-  const int grid = grid_for(n_words, MERGE_SCAN * 256, r);
+  const int r = use_lds ? resident_grid<k_merge<true>>(256, 64 * 1024, 2, q) : resident_grid<k_merge<false>>(256, 0, 4, q);
+  const int grid = blocks_for(n_words, MERGE_SCAN * 256, r);
   unsigned long long* sg = reinterpret_cast<unsigned long long*>(sig);
   if (use_lds)
-    hipLaunchKernelGGL(k_merge<true>, dim3(grid), dim3(256), lds, s, sym, wstart, wlen, wcount, n_words, a, b, new_id,
-                       tlen, max_token_length, deltas, Vt, sg);
-  else
-    hipLaunchKernelGGL(k_merge<false>, dim3(grid), dim3(256), 0, s, sym, wstart, wlen, wcount, n_words, a, b, new_id,
-                       tlen, max_token_length, deltas, Vt, sg);
-  BEAST_LAUNCHED("k_merge");
-  return BEAST_OK;
+    return launch<k_merge<true>>(grid, 256, lds, q, "k_merge", sym, wstart, wlen, wcount, n_words, a, b, new_id, tlen,
+                                 max_token_length, deltas, Vt, sg);
+  return launch<k_merge<false>>(grid, 256, 0, q, "k_merge", sym, wstart, wlen, wcount, n_words, a, b, new_id, tlen,
+                                max_token_length, deltas, Vt, sg);
 }
 
 // ---- device-driven loop: workspace = LoopState | hash table | token hashes | merge log
@@ -1545,9 +1545,10 @@ extern "C" int beast_bpe_loop_init(void* ws, size_t ws_bytes, int Vt, int max_me
                 "beast_bpe_loop_init: bad sizes");
   const LoopLayout L = loop_layout(Vt, max_merges);
   BEAST_REQUIRE_CODE(ws_bytes >= L.total, BEAST_E_WORKSPACE, "loop workspace %zu < %zu", ws_bytes, L.total);
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_loop_init"));
   unsigned char* w = static_cast<unsigned char*>(ws);
-  BEAST_HIP(hipMemsetAsync(w + L.lid, 0xFF, L.th - L.lid, s), "loop hash memset");
+  BEAST_HIP(hipMemsetAsync(w + L.lid, 0xFF, L.th - L.lid, q.s), "loop hash memset");
   LoopState init{};
   init.active = 1;
   init.vcur = n_tokens;
@@ -1557,12 +1558,10 @@ extern "C" int beast_bpe_loop_init(void* ws, size_t ws_bytes, int Vt, int max_me
   init.max_merges = max_merges;
   init.maxtlen = max_tlen;
   const int n = n_tokens > 0 ? n_tokens : 1;
-  hipLaunchKernelGGL(k_loop_init, dim3((n + 255) / 256), dim3(256), 0, s, reinterpret_cast<LoopState*>(w + L.st), init,
-                     loop_hash_view(ws, Vt, max_merges), n_tokens, init.log2cap,
-                     reinterpret_cast<const unsigned long long*>(tok_hash),
-                     reinterpret_cast<const unsigned long long*>(tok_pow), tlen);
-  BEAST_LAUNCHED("k_loop_init");
-  return BEAST_OK;
+  return launch<k_loop_init>((n + 255) / 256, 256, 0, q, "k_loop_init", reinterpret_cast<LoopState*>(w + L.st), init,
+                             loop_hash_view(ws, Vt, max_merges), n_tokens, init.log2cap,
+                             reinterpret_cast<const unsigned long long*>(tok_hash),
+                             reinterpret_cast<const unsigned long long*>(tok_pow), tlen);
 }
 
 extern "C" int beast_bpe_loop_state(const void* ws, int Vt, int max_merges, const void** state, const void** log) {
@@ -1579,11 +1578,9 @@ extern "C" size_t beast_bpe_batch_delta_count(int Vt) { return (size_t)BK * 4 * 
 
 template <int KM>
 static int launch_apply(LoopState* st, const LoopHash& lh, BatchWs bw, ArgWs aw, int Vt, uint32_t* tlen,
-                        uint32_t* table, int rows, int init, int32_t* deltas, hipStream_t s) {
-  hipLaunchKernelGGL(k_apply_batch<KM>, dim3((rows + APPLY_ROWS - 1) / APPLY_ROWS), dim3(64 * APPLY_ROWS), 0, s, table,
-                     Vt, aw, bw, tlen, st, lh, rows, init, deltas, (long long)beast::g_merge_lds_min);
-  BEAST_LAUNCHED("k_apply_batch");
-  return BEAST_OK;
+                        uint32_t* table, int rows, int init, int32_t* deltas, const Queue& q) {
+  return launch<k_apply_batch<KM>>((rows + APPLY_ROWS - 1) / APPLY_ROWS, 64 * APPLY_ROWS, 0, q, "k_apply_batch", table,
+                                   Vt, aw, bw, tlen, st, lh, rows, init, deltas, (long long)beast::g_merge_lds_min);
 }
 
 extern "C" int beast_bpe_loop_batch(void* ws, int Vt, int max_merges, int n_steps, int max_batch, int flags,
@@ -1600,7 +1597,8 @@ extern "C" int beast_bpe_loop_batch(void* ws, int Vt, int max_merges, int n_step
   BEAST_REQUIRE((flags & ~7) == 0, "beast_bpe_loop_batch: unknown flags %d", flags);
   BEAST_REQUIRE_CODE(batch_ws_bytes_ >= batch_ws_bytes(Vt), BEAST_E_WORKSPACE, "batch workspace %zu < %zu",
                      batch_ws_bytes_, batch_ws_bytes(Vt));
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_loop_batch"));
   const LoopLayout L = loop_layout(Vt, max_merges);
   LoopState* st = reinterpret_cast<LoopState*>(static_cast<unsigned char*>(ws) + L.st);
   const LoopHash lh = loop_hash_view(ws, Vt, max_merges);
@@ -1609,24 +1607,21 @@ extern "C" int beast_bpe_loop_batch(void* ws, int Vt, int max_merges, int n_step
   const int rows = std::min(Vt, std::max(vocab_size, 1));
   auto apply = [&](int init) {
     switch (max_batch) {
-      case 2: return launch_apply<2>(st, lh, bw, aw, Vt, tlen, table, rows, init, deltas, s);
-      case 4: return launch_apply<4>(st, lh, bw, aw, Vt, tlen, table, rows, init, deltas, s);
-      default: return launch_apply<8>(st, lh, bw, aw, Vt, tlen, table, rows, init, deltas, s);
+      case 2: return launch_apply<2>(st, lh, bw, aw, Vt, tlen, table, rows, init, deltas, q);
+      case 4: return launch_apply<4>(st, lh, bw, aw, Vt, tlen, table, rows, init, deltas, q);
+      default: return launch_apply<8>(st, lh, bw, aw, Vt, tlen, table, rows, init, deltas, q);
     }
   };
   if (flags & BEAST_BPE_BATCH_INIT) {   // every row's best and second-best, then the first batch
-    BEAST_HIP(hipMemsetAsync(batch_ws, 0, batch_ws_bytes(Vt), s), "batch workspace memset");
+    BEAST_HIP(hipMemsetAsync(batch_ws, 0, batch_ws_bytes(Vt), q.s), "batch workspace memset");
     if (int rc = apply(1)) return rc;
   }
-  static int resident = 0;
-  if (resident == 0) resident = resident_grid(k_merge_batch, 256, 0, 2);
-  const int grid = grid_for(n_words > 0 ? n_words : 1, MERGE_SCAN * 256, resident);
+  const int grid = blocks_for(n_words > 0 ? n_words : 1, MERGE_SCAN * 256, resident_grid<k_merge_batch>(256, 0, 2, q));
   for (int i = 0; i < n_steps; ++i) {
     if (!(flags & BEAST_BPE_BATCH_NO_MERGE)) {
-      hipLaunchKernelGGL(k_merge_batch, dim3(grid), dim3(256), 0, s, sym, wstart, wlen, wcount, n_words, tlen,
-                         max_token_length, Vt, reinterpret_cast<unsigned long long*>(sig), st, lh, table, aw.clean,
-                         deltas, apps);
-      BEAST_LAUNCHED("k_merge_batch");
+      BEAST_TRY(launch<k_merge_batch>(grid, 256, 0, q, "k_merge_batch", sym, wstart, wlen, wcount, n_words, tlen,
+                                      max_token_length, Vt, reinterpret_cast<unsigned long long*>(sig), st, lh, table,
+                                      aw.clean, deltas, apps));
     }
     if (!(flags & BEAST_BPE_BATCH_NO_APPLY))
       if (int rc = apply(0)) return rc;

@@ -18,6 +18,7 @@
 
 #include "bpe_common.h"
 #include "common.h"
+#include "launch.h"
 #include "pretok.h"
 
 namespace {
@@ -329,17 +330,14 @@ int64_t scan_ws_elems(int64_t n) {
   return total + 2;
 }
 
-int scan_rec(const int64_t* in, int64_t* out, int64_t n, int64_t* ws, hipStream_t s) {
+int scan_rec(const int64_t* in, int64_t* out, int64_t n, int64_t* ws, const Queue& q) {
   const int64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
   int64_t* sums = ws;
   int64_t* offs = ws + tiles;
-  hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(SCAN_T), 0, s, in, out, n, sums);
-  BEAST_LAUNCHED("k_scan_tiles");
+  BEAST_TRY(launch<k_scan_tiles>(tiles, SCAN_T, 0, q, "k_scan_tiles", in, out, n, sums));
   if (tiles > 1) {
-    int rc = scan_rec(sums, offs, tiles, ws + 2 * tiles + 1, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_scan_add, dim3(tiles), dim3(SCAN_T), 0, s, out, n, offs);
-    BEAST_LAUNCHED("k_scan_add");
+    BEAST_TRY(scan_rec(sums, offs, tiles, ws + 2 * tiles + 1, q));
+    BEAST_TRY(launch<k_scan_add>(tiles, SCAN_T, 0, q, "k_scan_add", out, n, offs));
   }
   return BEAST_OK;
 }
@@ -941,24 +939,22 @@ __global__ __launch_bounds__(256) void k_word_sig(const uint16_t* __restrict__ s
 // =================================================================== C-ABI ==
 extern "C" int beast_i64_minmax(const int64_t* x, int64_t n, int64_t* out2, void* stream) {
   BEAST_REQUIRE(x && out2 && n >= 1, "beast_i64_minmax: bad args");
-  hipStream_t s = beast::as_stream(stream);
-  hipLaunchKernelGGL(k_minmax_init, dim3(1), dim3(1), 0, s, reinterpret_cast<long long*>(out2));
-  hipLaunchKernelGGL(k_minmax, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, reinterpret_cast<const long long*>(x),
-                     n, reinterpret_cast<long long*>(out2));
-  BEAST_LAUNCHED("k_minmax");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_i64_minmax"));
+  BEAST_TRY(launch<k_minmax_init>(1, 1, 0, q, "k_minmax_init", reinterpret_cast<long long*>(out2)));
+  return launch<k_minmax>(blocks_for(n, 256, 2048), 256, 0, q, "k_minmax", reinterpret_cast<const long long*>(x), n,
+                          reinterpret_cast<long long*>(out2));
 }
 
 extern "C" int beast_bpe_cp_presence(const int64_t* tok, int64_t n, int64_t min_tok, uint8_t* present, int64_t n_cp,
                                      void* stream) {
   BEAST_REQUIRE(tok && present && n >= 0 && n_cp >= 1, "beast_bpe_cp_presence: bad args");
-  hipStream_t s = beast::as_stream(stream);
-  BEAST_HIP(hipMemsetAsync(present, 0, (size_t)n_cp, s), "presence memset");
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_cp_presence"));
+  BEAST_HIP(hipMemsetAsync(present, 0, (size_t)n_cp, q.s), "presence memset");
   if (n == 0) return BEAST_OK;
-  hipLaunchKernelGGL(k_presence, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s,
-                     reinterpret_cast<const long long*>(tok), n, (long long)min_tok, present, n_cp);
-  BEAST_LAUNCHED("k_presence");
-  return BEAST_OK;
+  return launch<k_presence>(blocks_for(n, 256, 2048), 256, 0, q, "k_presence", reinterpret_cast<const long long*>(tok), n,
+                            (long long)min_tok, present, n_cp);
 }
 
 extern "C" int beast_bpe_pretok_count(const int64_t* tok, const int64_t* seq_off, int64_t n_seq, int64_t min_tok,
@@ -966,26 +962,24 @@ extern "C" int beast_bpe_pretok_count(const int64_t* tok, const int64_t* seq_off
                                       int64_t* syms_per_seq, void* stream) {
   BEAST_REQUIRE(tok && seq_off && cls_lut && words_per_seq && syms_per_seq, "beast_bpe_pretok_count: null pointer");
   if (n_seq <= 0) return BEAST_OK;
-  hipLaunchKernelGGL(k_pretok_wave<false>, dim3(grid_for(n_seq, PT_WAVES, 16384)), dim3(64 * PT_WAVES), 0,
-                     beast::as_stream(stream),
-                     reinterpret_cast<const long long*>(tok), seq_off, n_seq, (long long)min_tok, cls_lut, lut_n,
-                     words_per_seq, syms_per_seq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  BEAST_LAUNCHED("k_pretok<count>");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_pretok_count"));
+  return launch<k_pretok_wave<false>>(blocks_for(n_seq, PT_WAVES, 16384), 64 * PT_WAVES, 0, q, "k_pretok<count>",
+                                      reinterpret_cast<const long long*>(tok), seq_off, n_seq, (long long)min_tok,
+                                      cls_lut, lut_n, words_per_seq, syms_per_seq, nullptr, nullptr, nullptr, nullptr,
+                                      nullptr, nullptr);
 }
 
 extern "C" size_t beast_scan_workspace_bytes(int64_t n) { return (size_t)scan_ws_elems(n) * sizeof(int64_t); }
 
 extern "C" int beast_exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, void* workspace, void* stream) {
   BEAST_REQUIRE(in && out && workspace && n >= 0, "beast_exclusive_scan_i64: bad args");
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_exclusive_scan_i64"));
   if (n > 0) {
-    int rc = scan_rec(in, out, n, reinterpret_cast<int64_t*>(workspace), s);
-    if (rc) return rc;
+    BEAST_TRY(scan_rec(in, out, n, reinterpret_cast<int64_t*>(workspace), q));
   }
-  hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, s, in, out, n);
-  BEAST_LAUNCHED("k_scan_total");
-  return BEAST_OK;
+  return launch<k_scan_total>(1, 64, 0, q, "k_scan_total", in, out, n);
 }
 
 extern "C" int beast_bpe_pretok_emit(const int64_t* tok, const int64_t* seq_off, int64_t n_seq, int64_t min_tok,
@@ -995,12 +989,11 @@ extern "C" int beast_bpe_pretok_emit(const int64_t* tok, const int64_t* seq_off,
   BEAST_REQUIRE(tok && seq_off && cls_lut && word_off && sym_off && byte2id && sym && wstart && wlen,
                 "beast_bpe_pretok_emit: null pointer");
   if (n_seq <= 0) return BEAST_OK;
-  hipLaunchKernelGGL(k_pretok_wave<true>, dim3(grid_for(n_seq, PT_WAVES, 16384)), dim3(64 * PT_WAVES), 0,
-                     beast::as_stream(stream),
-                     reinterpret_cast<const long long*>(tok), seq_off, n_seq, (long long)min_tok, cls_lut, lut_n,
-                     nullptr, nullptr, word_off, sym_off, byte2id, sym, wstart, wlen);
-  BEAST_LAUNCHED("k_pretok<emit>");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_pretok_emit"));
+  return launch<k_pretok_wave<true>>(blocks_for(n_seq, PT_WAVES, 16384), 64 * PT_WAVES, 0, q, "k_pretok<emit>",
+                                     reinterpret_cast<const long long*>(tok), seq_off, n_seq, (long long)min_tok,
+                                     cls_lut, lut_n, nullptr, nullptr, word_off, sym_off, byte2id, sym, wstart, wlen);
 }
 
 extern "C" int beast_bpe_count_pairs(const uint16_t* sym, const uint32_t* wstart, const uint32_t* wlen,
@@ -1009,41 +1002,30 @@ extern "C" int beast_bpe_count_pairs(const uint16_t* sym, const uint32_t* wstart
   BEAST_REQUIRE(sym && wstart && wlen && table && Vt >= 1 && Vt <= 65535, "beast_bpe_count_pairs: bad args");
   BEAST_REQUIRE(n_sym >= 0 && n_sym <= Vt, "beast_bpe_count_pairs: n_sym %d not in [0, Vt]", n_sym);
   if (n_words <= 0) return BEAST_OK;
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_count_pairs"));
   const size_t budget = 160 * 1024;
   const int R = n_sym > 0 ? (int)std::min<size_t>((size_t)n_sym, budget / (4 * (size_t)n_sym)) : 0;
   const int groups = R > 0 ? (n_sym + R - 1) / R : 0;
   if (R > 0 && groups <= 16) {   // LDS-privatised (the words are read once per row group)
     const size_t lds = (size_t)R * n_sym * 4;
-    if (lds > 65536)
-      BEAST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_count_pairs_lds),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                "hipFuncSetAttribute(k_count_pairs_lds)");
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
     const int per_cu = std::max(1, (int)(budget / std::max<size_t>(lds, 1)));
-    const int gx = std::max(1, std::min<int>(cus * per_cu / groups, (int)((n_words + 255) / 256)));
-    hipLaunchKernelGGL(k_count_pairs_lds, dim3(gx, groups), dim3(256), lds, s, sym, wstart, wlen, wcount, n_words,
-                       table, Vt, n_sym, R);
-    BEAST_LAUNCHED("k_count_pairs_lds");
-    return BEAST_OK;
+    const int gx = std::max(1, std::min<int>(cu_count(q.dev) * per_cu / groups, (int)((n_words + 255) / 256)));
+    return launch<k_count_pairs_lds>(dim3(gx, groups), 256, lds, q, "k_count_pairs_lds", sym, wstart, wlen, wcount,
+                                     n_words, table, Vt, n_sym, R);
   }
-  hipLaunchKernelGGL(k_count_pairs, dim3(grid_for(n_words, 256, 8192)), dim3(256), 0, s, sym,
-                     wstart, wlen, wcount, n_words, table, Vt);
-  BEAST_LAUNCHED("k_count_pairs");
-  return BEAST_OK;
+  return launch<k_count_pairs>(blocks_for(n_words, 256, 8192), 256, 0, q, "k_count_pairs", sym, wstart, wlen, wcount,
+                               n_words, table, Vt);
 }
 
 extern "C" int beast_bpe_word_signatures(const uint16_t* sym, const uint32_t* wstart, const uint32_t* wlen,
                                          int64_t n_words, uint64_t* sig, void* stream) {
   BEAST_REQUIRE(sym && wstart && wlen && sig && n_words >= 0, "beast_bpe_word_signatures: bad args");
   if (n_words == 0) return BEAST_OK;
-  hipLaunchKernelGGL(k_word_sig, dim3(grid_for(n_words, 256, 8192)), dim3(256), 0, beast::as_stream(stream), sym,
-                     wstart, wlen, n_words, reinterpret_cast<unsigned long long*>(sig));
-  BEAST_LAUNCHED("k_word_sig");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_word_signatures"));
+  return launch<k_word_sig>(blocks_for(n_words, 256, 8192), 256, 0, q, "k_word_sig", sym, wstart, wlen, n_words,
+                            reinterpret_cast<unsigned long long*>(sig));
 }
 
 extern "C" size_t beast_bpe_dedup_workspace_bytes(int64_t n_words) {
@@ -1064,7 +1046,8 @@ extern "C" int beast_bpe_dedup_words(const uint16_t* sym, const uint32_t* wstart
   BEAST_REQUIRE(n_words >= 0 && n_words < (int64_t(1) << 32) - 1, "beast_bpe_dedup_words: bad n_words");
   BEAST_REQUIRE_CODE(ws_bytes >= beast_bpe_dedup_workspace_bytes(n_words), BEAST_E_WORKSPACE,
                      "dedup workspace %zu < %zu", ws_bytes, beast_bpe_dedup_workspace_bytes(n_words));
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_dedup_words"));
   const int64_t n = n_words > 0 ? n_words : 1;
   DedupWs ws;
   ws.cap = 1024;   // the largest power of two the workspace holds
@@ -1076,18 +1059,14 @@ extern "C" int beast_bpe_dedup_words(const uint16_t* sym, const uint32_t* wstart
   ws.rep = reinterpret_cast<uint32_t*>(p);              p += n * 4;
   ws.slot = reinterpret_cast<uint32_t*>(p);             p += n * 4;
   ws.nu = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(p) + 7) & ~uintptr_t(7));
-  BEAST_HIP(hipMemsetAsync(workspace, 0, ws.cap * 12, s), "dedup memset");
-  BEAST_HIP(hipMemsetAsync(ws.nu, 0, 16, s), "dedup memset");
+  BEAST_HIP(hipMemsetAsync(workspace, 0, ws.cap * 12, q.s), "dedup memset");
+  BEAST_HIP(hipMemsetAsync(ws.nu, 0, 16, q.s), "dedup memset");
   if (n_words > 0) {
-    hipLaunchKernelGGL(k_dedup_insert, dim3(grid_for(n_words, DEDUP_T, 16384 * 256 / DEDUP_T)), dim3(DEDUP_T), 0, s,
-                       sym, wstart, wlen,
-                       n_words, ws);
-    BEAST_LAUNCHED("k_dedup_insert");
+    BEAST_TRY(launch<k_dedup_insert>(blocks_for(n_words, DEDUP_T, 16384 * 256 / DEDUP_T), DEDUP_T, 0, q, "k_dedup_insert",
+                                     sym, wstart, wlen, n_words, ws));
   }
-  hipLaunchKernelGGL(k_dedup_gather, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, wstart, wlen, ws, out_wstart,
-                     out_wlen, out_wcount, out_n);
-  BEAST_LAUNCHED("k_dedup_gather");
-  return BEAST_OK;
+  return launch<k_dedup_gather>(blocks_for(n, 256, 8192), 256, 0, q, "k_dedup_gather", wstart, wlen, ws, out_wstart,
+                                out_wlen, out_wcount, out_n);
 }
 
 // ---- one-pass setup (k_pretok_dedup): the table and the distinct-word list in one workspace
@@ -1120,23 +1099,24 @@ extern "C" int beast_bpe_pretok_dedup(const int64_t* tok, const int64_t* seq_off
                                       int64_t* out_info, void* stream) {
   BEAST_REQUIRE(tok && seq_off && cls_lut && workspace && out_info, "beast_bpe_pretok_dedup: null pointer");
   BEAST_REQUIRE(n_seq >= 0 && ws_bytes >= 1024 * PD_SLOT_BYTES + 64, "beast_bpe_pretok_dedup: bad sizes");
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_pretok_dedup"));
   PdWs w = pd_view(workspace, ws_bytes);
-  BEAST_HIP(hipMemsetAsync(w.keys, 0, w.cap * 12, s), "pretok_dedup memset");   // keys + counts
-  BEAST_HIP(hipMemsetAsync(w.info, 0, 32, s), "pretok_dedup memset");
+  BEAST_HIP(hipMemsetAsync(w.keys, 0, w.cap * 12, q.s), "pretok_dedup memset");   // keys + counts
+  BEAST_HIP(hipMemsetAsync(w.info, 0, 32, q.s), "pretok_dedup memset");
   if (n_seq > 0) {
     // the waves walk the sequences grid-stride; rows of <= 256 code points first (49 KB of LDS a
     // workgroup), rows of 257..512 by the 512 kernel only when some row needs it
-    hipLaunchKernelGGL(k_pretok_dedup<256>, dim3(grid_for(n_seq, PD_WAVES, PD_GRID * 256)), dim3(64 * PD_WAVES), 0, s,
-                       reinterpret_cast<const long long*>(tok), seq_off, n_seq, (long long)min_tok, cls_lut, lut_n, w);
-    BEAST_LAUNCHED("k_pretok_dedup<256>");
-    hipLaunchKernelGGL(k_pretok_dedup<PT_LC>, dim3(grid_for(n_seq, PD_WAVES, 2 * 256)), dim3(64 * PD_WAVES), 0, s,
-                       reinterpret_cast<const long long*>(tok), seq_off, n_seq, (long long)min_tok, cls_lut, lut_n, w);
-    BEAST_LAUNCHED("k_pretok_dedup<512>");
-    hipLaunchKernelGGL(k_pd_compact, dim3((unsigned)((w.cap + 256 * PDC_PER - 1) / (256 * PDC_PER))), dim3(256), 0, s, w);
-    BEAST_LAUNCHED("k_pd_compact");
+    BEAST_TRY(launch<k_pretok_dedup<256>>(blocks_for(n_seq, PD_WAVES, PD_GRID * 256), 64 * PD_WAVES, 0, q,
+                                          "k_pretok_dedup<256>", reinterpret_cast<const long long*>(tok), seq_off,
+                                          n_seq, (long long)min_tok, cls_lut, lut_n, w));
+    BEAST_TRY(launch<k_pretok_dedup<PT_LC>>(blocks_for(n_seq, PD_WAVES, 2 * 256), 64 * PD_WAVES, 0, q,
+                                            "k_pretok_dedup<512>", reinterpret_cast<const long long*>(tok), seq_off,
+                                            n_seq, (long long)min_tok, cls_lut, lut_n, w));
+    BEAST_TRY(launch<k_pd_compact>((unsigned)((w.cap + 256 * PDC_PER - 1) / (256 * PDC_PER)), 256, 0, q, "k_pd_compact",
+                                   w));
   }
-  BEAST_HIP(hipMemcpyAsync(out_info, w.info, 32, hipMemcpyDeviceToDevice, s), "pretok_dedup info");
+  BEAST_HIP(hipMemcpyAsync(out_info, w.info, 32, hipMemcpyDeviceToDevice, q.s), "pretok_dedup info");
   return BEAST_OK;
 }
 
@@ -1151,7 +1131,8 @@ extern "C" int beast_bpe_pretok_dedup_repack(const int64_t* tok, int64_t min_tok
   BEAST_REQUIRE(n_distinct >= 0 && (uint64_t)n_distinct <= w.cap, "beast_bpe_pretok_dedup_repack: bad n_distinct");
   BEAST_REQUIRE_CODE(repack_ws_bytes >= beast_bpe_repack_workspace_bytes(n_distinct) + 8 * (size_t)(n_distinct + 1),
                      BEAST_E_WORKSPACE, "repack workspace %zu too small", repack_ws_bytes);
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_pretok_dedup_repack"));
   const int64_t n = n_distinct > 0 ? n_distinct : 1;
   char* p = static_cast<char*>(repack_ws);
   uint32_t* hist = reinterpret_cast<uint32_t*>(p);   p += 256 * 4;
@@ -1164,26 +1145,24 @@ extern "C" int beast_bpe_pretok_dedup_repack(const int64_t* tok, int64_t min_tok
   p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 7) & ~uintptr_t(7));
   uint32_t* blen = reinterpret_cast<uint32_t*>(p);   p += n * 4;   // byte lengths / counts before the sort
   uint32_t* cnt = reinterpret_cast<uint32_t*>(p);
-  BEAST_HIP(hipMemsetAsync(hist, 0, 256 * 4, s), "repack memset");
+  BEAST_HIP(hipMemsetAsync(hist, 0, 256 * 4, q.s), "repack memset");
   if (n_distinct == 0) {
-    BEAST_HIP(hipMemsetAsync(out_nsym, 0, 8, s), "repack memset");
+    BEAST_HIP(hipMemsetAsync(out_nsym, 0, 8, q.s), "repack memset");
     return BEAST_OK;
   }
-  const int g = grid_for(n_distinct, 256, 8192);
-  hipLaunchKernelGGL(k_pd_gather, dim3(g), dim3(256), 0, s, w, n_distinct, blen, cnt);
-  hipLaunchKernelGGL(k_len_hist, dim3(g), dim3(256), 0, s, blen, n_distinct, hist);
-  hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(256), 0, s, hist, cursor);
-  hipLaunchKernelGGL(k_len_scatter, dim3((n_distinct + RP_WPB - 1) / RP_WPB), dim3(256), 0, s, blen, n_distinct, cursor,
-                     order);
-  hipLaunchKernelGGL(k_gather_lens, dim3(g), dim3(256), 0, s, order, blen, cnt, n_distinct, lens, out_wlen, out_wcount);
-  BEAST_LAUNCHED("k_gather_lens");
-  int rc = scan_rec(lens, offs, n_distinct, sws, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, s, lens, offs, n_distinct);
-  hipLaunchKernelGGL(k_copy_words_cp, dim3(g), dim3(256), 0, s, order, reinterpret_cast<const long long*>(tok),
-                     (long long)min_tok, byte2id, w.rep, w.lens, offs, n_distinct, out_sym, out_wstart, out_nsym);
-  BEAST_LAUNCHED("k_copy_words_cp");
-  return BEAST_OK;
+  const int g = blocks_for(n_distinct, 256, 8192);
+  BEAST_TRY(launch<k_pd_gather>(g, 256, 0, q, "k_pd_gather", w, n_distinct, blen, cnt));
+  BEAST_TRY(launch<k_len_hist>(g, 256, 0, q, "k_len_hist", blen, n_distinct, hist));
+  BEAST_TRY(launch<k_bucket_scan>(1, 256, 0, q, "k_bucket_scan", hist, cursor));
+  BEAST_TRY(launch<k_len_scatter>((n_distinct + RP_WPB - 1) / RP_WPB, 256, 0, q, "k_len_scatter", blen, n_distinct,
+                                  cursor, order));
+  BEAST_TRY(launch<k_gather_lens>(g, 256, 0, q, "k_gather_lens", order, blen, cnt, n_distinct, lens, out_wlen,
+                                  out_wcount));
+  BEAST_TRY(scan_rec(lens, offs, n_distinct, sws, q));
+  BEAST_TRY(launch<k_scan_total>(1, 64, 0, q, "k_scan_total", lens, offs, n_distinct));
+  return launch<k_copy_words_cp>(g, 256, 0, q, "k_copy_words_cp", order, reinterpret_cast<const long long*>(tok),
+                                 (long long)min_tok, byte2id, w.rep, w.lens, offs, n_distinct, out_sym, out_wstart,
+                                 out_nsym);
 }
 
 extern "C" int beast_bpe_compact_words(const uint32_t* wstart, const uint32_t* wlen, const uint32_t* wcount,
@@ -1192,12 +1171,13 @@ extern "C" int beast_bpe_compact_words(const uint32_t* wstart, const uint32_t* w
   BEAST_REQUIRE(wstart && wlen && out_wstart && out_wlen && out_wcount && out_n,
                 "beast_bpe_compact_words: null pointer");
   BEAST_REQUIRE(n_words >= 0, "beast_bpe_compact_words: bad n_words");
-  hipStream_t s = beast::as_stream(stream);
-  BEAST_HIP(hipMemsetAsync(out_n, 0, 8, s), "compact memset");
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_compact_words"));
+  BEAST_HIP(hipMemsetAsync(out_n, 0, 8, q.s), "compact memset");
   if (n_words > 0) {
-    hipLaunchKernelGGL(k_compact_words, dim3(grid_for(n_words, 256, 16384)), dim3(256), 0, s, wstart, wlen, wcount,
-                       n_words, out_wstart, out_wlen, out_wcount, reinterpret_cast<unsigned long long*>(out_n));
-    BEAST_LAUNCHED("k_compact_words");
+    BEAST_TRY(launch<k_compact_words>(blocks_for(n_words, 256, 16384), 256, 0, q, "k_compact_words", wstart, wlen, wcount,
+                                      n_words, out_wstart, out_wlen, out_wcount,
+                                      reinterpret_cast<unsigned long long*>(out_n)));
   }
   return BEAST_OK;
 }
@@ -1216,7 +1196,8 @@ extern "C" int beast_bpe_repack_words(const uint16_t* sym, const uint32_t* wstar
   BEAST_REQUIRE(n_words >= 0 && n_words < (int64_t(1) << 31), "beast_bpe_repack_words: bad n_words");
   BEAST_REQUIRE_CODE(ws_bytes >= beast_bpe_repack_workspace_bytes(n_words), BEAST_E_WORKSPACE,
                      "repack workspace %zu < %zu", ws_bytes, beast_bpe_repack_workspace_bytes(n_words));
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_repack_words"));
   const int64_t n = n_words > 0 ? n_words : 1;
   char* p = static_cast<char*>(workspace);
   uint32_t* hist = reinterpret_cast<uint32_t*>(p);   p += 256 * 4;
@@ -1226,23 +1207,20 @@ extern "C" int beast_bpe_repack_words(const uint16_t* sym, const uint32_t* wstar
   int64_t* lens = reinterpret_cast<int64_t*>(p);     p += n * 8;
   int64_t* offs = reinterpret_cast<int64_t*>(p);     p += (n + 1) * 8;
   int64_t* sws = reinterpret_cast<int64_t*>(p);
-  BEAST_HIP(hipMemsetAsync(hist, 0, 256 * 4, s), "repack memset");
+  BEAST_HIP(hipMemsetAsync(hist, 0, 256 * 4, q.s), "repack memset");
   if (n_words == 0) {
-    BEAST_HIP(hipMemsetAsync(out_nsym, 0, 8, s), "repack memset");
+    BEAST_HIP(hipMemsetAsync(out_nsym, 0, 8, q.s), "repack memset");
     return BEAST_OK;
   }
-  const int g = grid_for(n_words, 256, 8192);
-  hipLaunchKernelGGL(k_len_hist, dim3(g), dim3(256), 0, s, wlen, n_words, hist);
-  hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(256), 0, s, hist, cursor);
-  hipLaunchKernelGGL(k_len_scatter, dim3((n_words + RP_WPB - 1) / RP_WPB), dim3(256), 0, s, wlen, n_words, cursor, order);
-  hipLaunchKernelGGL(k_gather_lens, dim3(g), dim3(256), 0, s, order, wlen, wcount, n_words, lens, out_wlen,
-                     out_wcount);
-  BEAST_LAUNCHED("k_gather_lens");
-  int rc = scan_rec(lens, offs, n_words, sws, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, s, lens, offs, n_words);
-  hipLaunchKernelGGL(k_copy_words, dim3(g), dim3(256), 0, s, order, sym, wstart, wlen, offs, n_words, out_sym,
-                     out_wstart, out_nsym);
-  BEAST_LAUNCHED("k_copy_words");
-  return BEAST_OK;
+  const int g = blocks_for(n_words, 256, 8192);
+  BEAST_TRY(launch<k_len_hist>(g, 256, 0, q, "k_len_hist", wlen, n_words, hist));
+  BEAST_TRY(launch<k_bucket_scan>(1, 256, 0, q, "k_bucket_scan", hist, cursor));
+  BEAST_TRY(launch<k_len_scatter>((n_words + RP_WPB - 1) / RP_WPB, 256, 0, q, "k_len_scatter", wlen, n_words, cursor,
+                                  order));
+  BEAST_TRY(launch<k_gather_lens>(g, 256, 0, q, "k_gather_lens", order, wlen, wcount, n_words, lens, out_wlen,
+                                  out_wcount));
+  BEAST_TRY(scan_rec(lens, offs, n_words, sws, q));
+  BEAST_TRY(launch<k_scan_total>(1, 64, 0, q, "k_scan_total", lens, offs, n_words));
+  return launch<k_copy_words>(g, 256, 0, q, "k_copy_words", order, sym, wstart, wlen, offs, n_words, out_sym,
+                              out_wstart, out_nsym);
 }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -125,7 +126,8 @@ __global__ void k_offset_starts(uint32_t* __restrict__ w, int64_t n, uint32_t of
 // table grows 4x while it overflows) and their length-ordered repack
 int shard_words(DevMem& mem, const int64_t* tokens, const int64_t* seq_off, int64_t n_seq, int64_t mn,
                 const uint8_t* cls_lut, int64_t lut_n, const uint16_t* byte2id, uint16_t*& sym2, uint32_t*& w2,
-                uint32_t*& l2, uint32_t*& c2, int64_t& nu, int64_t& nsp, hipStream_t s) {
+                uint32_t*& l2, uint32_t*& c2, int64_t& nu, int64_t& nsp, const Queue& q) {
+  const hipStream_t s = q.s;
   void* stream = s;
   ALLOC(wps, int64_t, n_seq);
   ALLOC(sps, int64_t, n_seq);
@@ -185,7 +187,8 @@ int shard_words(DevMem& mem, const int64_t* tokens, const int64_t* seq_off, int6
 // array.  A word repeated across shards appears once per shard with its shard count, which
 // leaves every pair count (and so every merge) unchanged.
 int union_words(DevMem& mem, beast_comm* comm, uint16_t*& sym2, uint32_t*& w2, uint32_t*& l2, uint32_t*& c2,
-                int64_t& nu, int64_t& nsp, hipStream_t s) {
+                int64_t& nu, int64_t& nsp, const Queue& q) {
+  const hipStream_t s = q.s;
   void* stream = s;
   int world = 0, rank = 0;
   TRY(beast_comm_info(comm, &world, &rank, nullptr));
@@ -235,9 +238,8 @@ int union_words(DevMem& mem, beast_comm* comm, uint16_t*& sym2, uint32_t*& w2, u
   // local from here on: the caller agrees before its next collective
   for (int r = 0; r < world; ++r)
     if (wc[r] > 0 && bd[r] > 0) {
-      hipLaunchKernelGGL(k_offset_starts, dim3((unsigned)((wc[r] + 255) / 256)), dim3(256), 0, s, gw + wd[r], wc[r],
-                         (uint32_t)(bd[r] / 2));
-      BEAST_LAUNCHED("k_offset_starts");
+      BEAST_TRY(launch<k_offset_starts>((unsigned)((wc[r] + 255) / 256), 256, 0, q, "k_offset_starts", gw + wd[r],
+                                        wc[r], (uint32_t)(bd[r] / 2)));
     }
   const size_t rp_bytes = beast_bpe_repack_workspace_bytes(NU);
   ALLOC(rp_ws, uint8_t, rp_bytes);
@@ -271,8 +273,9 @@ static int bpe_train_impl(const int64_t* tokens, const int64_t* seq_off, int64_t
                           int64_t* out_max_token, char* out_vocab_bytes, size_t vocab_bytes_cap,
                           int64_t* out_vocab_off, int max_vocab, int* out_n_vocab, int32_t* out_merges,
                           int max_merges_out, int* out_n_merges, beast_comm* comm, bool replicate,
-                          bool host_loop, void* stream) {
-  hipStream_t s = beast::as_stream(stream);
+                          bool host_loop, const Queue& q) {
+  const hipStream_t s = q.s;
+  void* stream = s;
   DevMem mem;
   // ---- arguments, this shard's token count
   int64_t n_tok = 0;
@@ -402,11 +405,11 @@ static int bpe_train_impl(const int64_t* tokens, const int64_t* seq_off, int64_t
                          "required sizes are in *out_n_vocab, *out_n_merges",
                          max_vocab, max_merges_out, Vt);
     }
-    if (n_tok > 0) TRY(shard_words(mem, tokens, seq_off, n_seq, mn, cls_lut, lut_n, byte2id, sym2, w2, l2, c2, nu, nsp, s));
+    if (n_tok > 0) TRY(shard_words(mem, tokens, seq_off, n_seq, mn, cls_lut, lut_n, byte2id, sym2, w2, l2, c2, nu, nsp, q));
     return BEAST_OK;
   }());
   const bool sharded = comm != nullptr && !replicate;   // every rank keeps its shard of the words
-  if (comm != nullptr && replicate) TRY(union_words(mem, comm, sym2, w2, l2, c2, nu, nsp, s));
+  if (comm != nullptr && replicate) TRY(union_words(mem, comm, sym2, w2, l2, c2, nu, nsp, q));
 
   // ---- the pair table and the loop state
   uint64_t* sig = nullptr;
@@ -690,12 +693,18 @@ static int bpe_train_entry(const int64_t* tokens, const int64_t* seq_off, int64_
                            int64_t* out_max_token, char* out_vocab_bytes, size_t vocab_bytes_cap,
                            int64_t* out_vocab_off, int max_vocab, int* out_n_vocab, int32_t* out_merges,
                            int max_merges_out, int* out_n_merges, beast_comm* comm, bool replicate, void* stream) {
+  // everything below -- the internal allocations, and the destructors of bpe_train_impl's DevMem and
+  // HostPinned -- runs with the stream's device current; the caller's is restored on return
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bpe_train"));
+  const DeviceGuard on(q.dev);
+  BEAST_HIP(on.status(), "beast_bpe_train");
   int rc = RERUN;
   for (int attempt = 0; attempt < 2 && rc == RERUN; ++attempt)
     rc = bpe_train_impl(tokens, seq_off, n_seq, cls_lut, lut_n, vocab_size, min_frequency, max_token_length,
                         special_tokens, n_special, out_min_token, out_max_token, out_vocab_bytes, vocab_bytes_cap,
                         out_vocab_off, max_vocab, out_n_vocab, out_merges, max_merges_out, out_n_merges, comm,
-                        replicate, attempt == 1, stream);
+                        replicate, attempt == 1, q);
   return rc;
 }
 

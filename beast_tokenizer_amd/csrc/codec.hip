@@ -2,8 +2,9 @@
 // the C-ABI entry points and the options.  One translation unit (the kernarg-preload flag, the
 // -DBEAST_STAMPS device globals and the code-object comparison depend on that), in layers:
 //
-//   launch.h             host only, shared with deriv.hip: the stream's device, cu_count, grid_for,
-//                        the debug knobs and launch_fn (cached handles, dynamic-LDS grant)
+//   launch.h             host only, the whole library's launch layer: the stream's device, DeviceGuard,
+//                        cu_count, grid_for, the debug knobs and the typed launch<kernel> (cached
+//                        handles, dynamic-LDS grant)
 //   codec_device.h       device primitives that know no argument block: FastDiv, LDS-DMA
 //                        staging, st16 store policies, stamps, Geom / Shape / Dims, and the single
 //                        definitions of the arithmetic the kernels must agree on bit for bit
@@ -102,11 +103,9 @@ int launch_encode_vw(EncArgs a, bool lat, const Queue& q) {
   a.g = make_geom<W>(S::D, S::NJ, S::N, S::T);
   a.ntiles = (a.B + W - 1) / W;
   mark_launch(launch_mark(FAM_ENCODE_V, W, W, 0, true, false, true, lat));
-  static FnCache fn = {};
-  return launch_fn(reinterpret_cast<const void*>(&k_encode_v<S, SP, W>), fn, (unsigned)a.ntiles, W * 64, L.total, q,
-                   "k_encode_v", a.traj, a.B,
-                   EncVArgs{a.dof_src, a.proj, a.w_min, a.w_max, a.tokens_out, a.params_out, a.tok_offset, a.vocab,
-                            a.phases});
+  return launch<k_encode_v<S, SP, W>>((unsigned)a.ntiles, W * 64, L.total, q, "k_encode_v", a.traj, a.B,
+                                      EncVArgs{a.dof_src, a.proj, a.w_min, a.w_max, a.tokens_out, a.params_out,
+                                               a.tok_offset, a.vocab, a.phases});
 }
 
 // write-through stores and RV_WE-wave tiles in the latency regime (at most one 16-trajectory tile
@@ -126,10 +125,8 @@ int launch_encode_t(EncArgs a, int T, int D, int nj, int N, bool fast, const Que
   BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "encode tile needs %d B of LDS", L.total);
   const int64_t grid = grid_for(a.ntiles, L.total, q.dev);
   mark_launch(launch_mark(S::fixed ? FAM_ENCODE_SPEC : FAM_ENCODE_DYN, TBT, S::W, 0, fast, false, true, S::W == 7));
-  static FnCache fn[2] = {};
-  return launch_fn(fast ? reinterpret_cast<const void*>(&k_encode<TBT, true, S>)
-                        : reinterpret_cast<const void*>(&k_encode<TBT, false, S>),
-                   fn[fast ? 1 : 0], (unsigned)grid, S::W * 64, L.total, q, "k_encode", a);
+  return fast ? launch<k_encode<TBT, true, S>>((unsigned)grid, S::W * 64, L.total, q, "k_encode", a)
+              : launch<k_encode<TBT, false, S>>((unsigned)grid, S::W * 64, L.total, q, "k_encode", a);
 }
 
 int enc_smem_total(int tbt, int T, int Dl, int D, int N, int nkinds) {
@@ -192,17 +189,14 @@ int launch_rec_ks(RecArgs a, int D, int nj, const Queue& q) {
   const RecSmem L = rec_smem<TBT, KS, RT>(a.Tout, D, a.g.N, a.ndo, nj < D ? 2 : 1, a.lut_n);
   BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "reconstruct tile needs %d B of LDS", L.total);
   const int64_t grid = grid_for(a.ntiles, L.total, q.dev);
-  static FnCache fn = {};
   if constexpr (KS == 0) {
     mark_launch(launch_mark(FAM_REC_ROWS, TBT, NWAVES, 0, false, false, L.stage, false));
-    return launch_fn(reinterpret_cast<const void*>(&k_reconstruct_rows<TBT>), fn, (unsigned)grid, NTHREADS, L.total,
-                     q, "k_reconstruct_rows", a);
+    return launch<k_reconstruct_rows<TBT>>((unsigned)grid, NTHREADS, L.total, q, "k_reconstruct_rows", a);
   } else {
     mark_launch(launch_mark(S::fixed ? FAM_REC_SPEC : FAM_REC_MFMA, TBT, S::W, KS, false, RT > 0, true, S::W == 7));
-    return launch_fn(reinterpret_cast<const void*>(&k_reconstruct<TBT, KS, RT, S>), fn, (unsigned)grid, S::W * 64,
-                     L.total, q, "k_reconstruct",
-                     a.ntokens ? static_cast<const void*>(a.ntokens) : static_cast<const void*>(a.tokens), a.B,
-                     a.ntokens ? 4 : 8, a);
+    return launch<k_reconstruct<TBT, KS, RT, S>>(
+        (unsigned)grid, S::W * 64, L.total, q, "k_reconstruct",
+        a.ntokens ? static_cast<const void*>(a.ntokens) : static_cast<const void*>(a.tokens), a.B, a.ntokens ? 4 : 8, a);
   }
 }
 
@@ -231,15 +225,13 @@ int launch_rec_v(RecArgs a, const Queue& q) {
   static_assert(L.total <= (RV_WR <= 8 ? 64 : 160) * 1024, "k_reconstruct_v LDS");
   a.tbt = RV_WR;
   a.ntiles = (a.B + RV_WR - 1) / RV_WR;
-  static FnCache fn[2] = {};
-  const bool lat = a.B <= 16 * (int64_t)cu_count(q.dev);   // <= 2 eight-trajectory tiles per CU
+  const bool lat = a.B <= 16 * (int64_t)cu_count(q.dev);   // at most one 16-trajectory tile per CU
   mark_launch(launch_mark(FAM_REC_V, RV_WR, RV_WR, KS, false, true, true, lat));
-  return launch_fn(lat ? reinterpret_cast<const void*>(&k_reconstruct_v<KS, S, LAT_SP>)
-                       : reinterpret_cast<const void*>(&k_reconstruct_v<KS, S, 0>),
-                   fn[lat ? 1 : 0], (unsigned)a.ntiles, RV_WR * 64, L.total, q, "k_reconstruct_v",
-                   static_cast<const void*>(a.tokens), a.B, 8,
-                   RecVArgs{a.w_min, a.w_max, a.basis, a.dof_dst, a.init_p, a.init_p_src, a.pos_out, a.tok_offset,
-                            a.init_p_sb, a.vocab, a.lut_n, a.phases});
+  const RecVArgs v{a.w_min, a.w_max, a.basis, a.dof_dst, a.init_p, a.init_p_src, a.pos_out, a.tok_offset,
+                   a.init_p_sb, a.vocab, a.lut_n, a.phases};
+  const unsigned grid = (unsigned)a.ntiles;
+  return lat ? launch<k_reconstruct_v<KS, S, LAT_SP>>(grid, RV_WR * 64, L.total, q, "k_reconstruct_v", a.tokens, a.B, 8, v)
+             : launch<k_reconstruct_v<KS, S, 0>>(grid, RV_WR * 64, L.total, q, "k_reconstruct_v", a.tokens, a.B, 8, v);
 }
 
 // Shared-basis positions run on the MFMA (k_reconstruct*) while the padded output tile fits LDS,
@@ -282,9 +274,7 @@ int launch_roundtrip(const float* traj, int64_t B, RtArgs a, int W, const Queue&
   const RtSmem L = rt_smem(a.T, a.D, a.N, a.nj < a.D ? 2 : 1, W, a.lut_n);
   BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "round trip tile needs %d B of LDS", L.total);
   const int64_t grid = grid_for((B + W - 1) / W, L.total, q.dev);
-  static FnCache fn = {};
-  return launch_fn(reinterpret_cast<const void*>(&k_roundtrip<S, WF>), fn, (unsigned)grid, (unsigned)(W * 64),
-                   (unsigned)L.total, q, "k_roundtrip", traj, B, a);
+  return launch<k_roundtrip<S, WF>>((unsigned)grid, (unsigned)(W * 64), (unsigned)L.total, q, "k_roundtrip", traj, B, a);
 }
 
 // 16-wave tiles while the batch gives every CU at most one, 8-wave tiles (three workgroups per CU

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -143,12 +144,9 @@ bool op_of(int op, ncclRedOp_t* out) {
 
 // a scratch int32[4] on `device` (the current device is restored)
 int alloc_scratch(int device, int32_t** out) {
-  int prev = 0;
-  BEAST_HIP(hipGetDevice(&prev), "hipGetDevice");
-  BEAST_HIP(hipSetDevice(device), "hipSetDevice");
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(out), 4 * sizeof(int32_t));
-  (void)hipSetDevice(prev);
-  BEAST_HIP(e, "communicator scratch");
+  const DeviceGuard on(device);
+  BEAST_HIP(on.status(), "communicator device");
+  BEAST_HIP(hipMalloc(reinterpret_cast<void**>(out), 4 * sizeof(int32_t)), "communicator scratch");
   return BEAST_OK;
 }
 
@@ -262,14 +260,13 @@ extern "C" int beast_comm_init_rank(int world, int rank, const void* id, int dev
   if (int rc = alloc_scratch(device, &scratch)) return rc;
   // RCCL binds the communicator to the current device: switch for the init, then restore the
   // caller's
-  int prev = 0;
-  BEAST_HIP(hipGetDevice(&prev), "hipGetDevice");
-  BEAST_HIP(hipSetDevice(device), "hipSetDevice");
+  const DeviceGuard on(device);
+  if (on.status() != hipSuccess) (void)hipFree(scratch);
+  BEAST_HIP(on.status(), "communicator device");
   ncclUniqueId uid;
   std::memcpy(&uid, id, sizeof(uid));
   ncclComm_t nc = nullptr;
   const ncclResult_t r = R->init_rank(&nc, world, uid, rank);
-  (void)hipSetDevice(prev);
   if (r != ncclSuccess) (void)hipFree(scratch);
   BEAST_NCCL(r, "ncclCommInitRank");
   *out = new beast_comm{nc, world, rank, device, nullptr, scratch};

@@ -161,8 +161,8 @@ __device__ __forceinline__ float denormalize_one(float x, float lo, float hi) {
     if (_e != hipSuccess) return beast::hip_fail(_e, what);       \
   } while (0)
 
-#define BEAST_LAUNCHED(what)                                      \
+// returns a failed step's status (variadic: a launch<k<A, B>>(...) holds top-level commas)
+#define BEAST_TRY(...)                                            \
   do {                                                            \
-    hipError_t _e = hipGetLastError();                            \
-    if (_e != hipSuccess) return beast::hip_fail(_e, what);       \
+    if (const int _rc = (__VA_ARGS__)) return _rc;                \
   } while (0)

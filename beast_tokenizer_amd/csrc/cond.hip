@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -120,13 +121,12 @@ extern "C" int beast_cond_fixed_f32(const float* traj, int64_t B, int T, int64_t
   BEAST_REQUIRE(init_order == 0 || (init_pos && init_vel && params_init), "beast_cond_fixed_f32: null init output");
   BEAST_REQUIRE(end_order == 0 || (end_pos && end_vel && params_end), "beast_cond_fixed_f32: null end output");
   if (B == 0 || dj == 0) return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_cond_fixed_f32"));
   const CondArgs c{init_order, end_order, degree, n_ctrl, tau};
   const int64_t n = B * dj;
-  hipLaunchKernelGGL(k_cond_fixed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, beast::as_stream(stream), traj, B,
-                     T, sb, st, sd, joint_idx, dj, times, knots, c, init_pos, init_vel, end_pos, end_vel, params_init,
-                     params_end);
-  BEAST_LAUNCHED("k_cond_fixed");
-  return BEAST_OK;
+  return launch<k_cond_fixed>((unsigned)((n + 255) / 256), 256, 0, q, "k_cond_fixed", traj, B, T, sb, st, sd, joint_idx,
+                              dj, times, knots, c, init_pos, init_vel, end_pos, end_vel, params_init, params_end);
 }
 
 extern "C" int beast_cond_add_f32(float* pos, int64_t B, int T, int D, const int32_t* joint_idx, int dj,
@@ -142,10 +142,10 @@ extern "C" int beast_cond_add_f32(float* pos, int64_t B, int T, int D, const int
   BEAST_REQUIRE(init_order == 0 || (params_init && init_pos), "beast_cond_add_f32: null init condition");
   BEAST_REQUIRE(end_order == 0 || params_end, "beast_cond_add_f32: null end condition");
   if (B == 0 || T == 0 || dj == 0) return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_cond_add_f32"));
   const CondArgs c{init_order, end_order, 0, n_ctrl, 0.0f};
   const int64_t n = B * T * dj;
-  hipLaunchKernelGGL(k_cond_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, beast::as_stream(stream), pos, B, T,
-                     D, joint_idx, dj, full_basis, full_sb, c, params_init, params_end, init_pos);
-  BEAST_LAUNCHED("k_cond_add");
-  return BEAST_OK;
+  return launch<k_cond_add>((unsigned)((n + 255) / 256), 256, 0, q, "k_cond_add", pos, B, T, D, joint_idx, dj,
+                            full_basis, full_sb, c, params_init, params_end, init_pos);
 }

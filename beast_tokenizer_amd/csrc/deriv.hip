@@ -235,9 +235,7 @@ int launch_derivs(DerivArgs a, int phi_bytes, int cus, const Queue& q) {
   // grid_for's cap, which lets a second round of workgroups queue up)
   const int per_cu = std::max(1, std::min(8, (160 * 1024) / std::max(lds, 1)));
   const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(a.ntiles, (int64_t)cus * per_cu));
-  static FnCache fn = {};
-  return launch_fn(reinterpret_cast<const void*>(&k_reconstruct_derivs<KS, LB, TB>), fn, (unsigned)grid, DV_THREADS,
-                   lds, q, "k_reconstruct_derivs", a);
+  return launch<k_reconstruct_derivs<KS, LB, TB>>((unsigned)grid, DV_THREADS, lds, q, "k_reconstruct_derivs", a);
 }
 
 template <int KS>

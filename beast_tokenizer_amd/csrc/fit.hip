@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -212,16 +213,16 @@ extern "C" int beast_bspline_basis_f32(const float* times, int64_t n_times, floa
   if (n_times <= 0) return BEAST_OK;
   const int nthr = 256;
   const int64_t nblk = (n_times + nthr - 1) / nthr;
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bspline_basis_f32"));
 #define BEAST_BASIS_CASE(K) \
-  case K: hipLaunchKernelGGL(k_basis<K>, dim3(nblk), dim3(nthr), 0, s, times, n_times, tau, delay, knots, num_basis, basis_out); break;
+  case K: return launch<k_basis<K>>(nblk, nthr, 0, q, "k_basis", times, n_times, tau, delay, knots, num_basis, basis_out);
   switch (degree) {
     BEAST_BASIS_CASE(0) BEAST_BASIS_CASE(1) BEAST_BASIS_CASE(2) BEAST_BASIS_CASE(3) BEAST_BASIS_CASE(4)
     BEAST_BASIS_CASE(5) BEAST_BASIS_CASE(6) BEAST_BASIS_CASE(7) BEAST_BASIS_CASE(8)
   }
 #undef BEAST_BASIS_CASE
-  BEAST_LAUNCHED("k_basis");
-  return BEAST_OK;
+  return BEAST_OK;   // unreachable: degree is in [0, 8]
 }
 
 extern "C" int beast_bspline_basis_deriv_f32(const float* times, int64_t n_times, float tau, float delay,
@@ -236,38 +237,35 @@ extern "C" int beast_bspline_basis_deriv_f32(const float* times, int64_t n_times
                 n_knots);
   BEAST_REQUIRE(n_times >= 0, "beast_bspline_basis_deriv_f32: n_times=%lld must be >= 0", (long long)n_times);
   if (n_times == 0) return BEAST_OK;
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bspline_basis_deriv_f32"));
   if (order > degree) {   // the spline's pieces have degree < order
-    BEAST_HIP(hipMemsetAsync(basis_out, 0, (size_t)n_times * num_basis * sizeof(float), s), "basis_deriv memset");
+    BEAST_HIP(hipMemsetAsync(basis_out, 0, (size_t)n_times * num_basis * sizeof(float), q.s), "basis_deriv memset");
     return BEAST_OK;
   }
   const int nthr = 256;
   const int64_t nblk = (n_times + nthr - 1) / nthr;
-#define BEAST_DERIV_CASE(K)                                                                                      \
-  case K:                                                                                                        \
-    if (order == 1)                                                                                              \
-      hipLaunchKernelGGL((k_basis_deriv<K, 1>), dim3(nblk), dim3(nthr), 0, s, times, n_times, tau, delay, knots, \
-                         num_basis, basis_out);                                                                  \
-    else                                                                                                         \
-      hipLaunchKernelGGL((k_basis_deriv<K, 2>), dim3(nblk), dim3(nthr), 0, s, times, n_times, tau, delay, knots, \
-                         num_basis, basis_out);                                                                  \
-    break;
+#define BEAST_DERIV_CASE(K)                                                                                       \
+  case K:                                                                                                         \
+    return order == 1 ? launch<k_basis_deriv<K, 1>>(nblk, nthr, 0, q, "k_basis_deriv", times, n_times, tau, delay, \
+                                                    knots, num_basis, basis_out)                                  \
+                      : launch<k_basis_deriv<K, 2>>(nblk, nthr, 0, q, "k_basis_deriv", times, n_times, tau, delay, \
+                                                    knots, num_basis, basis_out);
   switch (degree) {
     BEAST_DERIV_CASE(1) BEAST_DERIV_CASE(2) BEAST_DERIV_CASE(3) BEAST_DERIV_CASE(4)
     BEAST_DERIV_CASE(5) BEAST_DERIV_CASE(6) BEAST_DERIV_CASE(7) BEAST_DERIV_CASE(8)
   }
 #undef BEAST_DERIV_CASE
-  BEAST_LAUNCHED("k_basis_deriv");
-  return BEAST_OK;
+  return BEAST_OK;   // unreachable: 1 <= order <= degree <= 8
 }
 
 extern "C" int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, double* proj_out,
                                             void* stream) {
   BEAST_REQUIRE(basis && proj_out, "beast_bspline_projection_f64: null pointer");
   BEAST_REQUIRE(N >= 1 && N <= 16 && T >= 1, "projection: need 1 <= N <= 16, T >= 1 (N=%d T=%d)", N, T);
-  hipLaunchKernelGGL(k_projection, dim3(1), dim3(256), 0, beast::as_stream(stream), basis, T, N, reg, proj_out);
-  BEAST_LAUNCHED("k_projection");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_bspline_projection_f64"));
+  return launch<k_projection>(1, 256, 0, q, "k_projection", basis, T, N, reg, proj_out);
 }
 
 extern "C" int beast_quantize_f32(const float* params, int64_t B, int D, int N, const float* w_min,
@@ -277,12 +275,12 @@ extern "C" int beast_quantize_f32(const float* params, int64_t B, int D, int N, 
   BEAST_REQUIRE((mode == 0 && tokens_out && vocab >= 2) || (mode == 1 && ntok_out), "beast_quantize_f32: bad mode");
   BEAST_REQUIRE(B >= 0, "batch size B=%lld must be >= 0", (long long)B);
   if (B == 0) return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_quantize_f32"));
   const int64_t total = B * (int64_t)N * D;
   const int64_t grid = std::min<int64_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(k_quantize, dim3(grid), dim3(256), 0, beast::as_stream(stream), params, B, D, N, w_min, w_max,
-                     vocab, tok_offset, mode, reinterpret_cast<long long*>(tokens_out), ntok_out);
-  BEAST_LAUNCHED("k_quantize");
-  return BEAST_OK;
+  return launch<k_quantize>(grid, 256, 0, q, "k_quantize", params, B, D, N, w_min, w_max, vocab, tok_offset, mode,
+                            reinterpret_cast<long long*>(tokens_out), ntok_out);
 }
 
 extern "C" size_t beast_colminmax_workspace_bytes(int64_t rows, int cols) {
@@ -300,11 +298,10 @@ extern "C" int beast_colminmax_f32(const float* x, int64_t rows, int cols, int64
   const int nblk = (int)((rows + rpb - 1) / rpb);
   float* pmin = reinterpret_cast<float*>(workspace);
   float* pmax = pmin + (size_t)MINMAX_BLOCKS * cols;
-  hipStream_t s = beast::as_stream(stream);
-  hipLaunchKernelGGL(k_colminmax_partial, dim3(nblk), dim3(256), 0, s, x, rows, cols, row_stride, rpb, pmin, pmax);
-  BEAST_LAUNCHED("k_colminmax_partial");
-  hipLaunchKernelGGL(k_colminmax_final, dim3((cols + 255) / 256), dim3(256), 0, s, pmin, pmax, nblk, cols, out_min,
-                     out_max);
-  BEAST_LAUNCHED("k_colminmax_final");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_colminmax_f32"));
+  BEAST_TRY(launch<k_colminmax_partial>(nblk, 256, 0, q, "k_colminmax_partial", x, rows, cols, row_stride, rpb, pmin,
+                                        pmax));
+  return launch<k_colminmax_final>((cols + 255) / 256, 256, 0, q, "k_colminmax_final", pmin, pmax, nblk, cols, out_min,
+                                   out_max);
 }

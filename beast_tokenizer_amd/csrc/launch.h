@@ -1,6 +1,6 @@
-// Host-only launch layer of codec.hip and deriv.hip: the stream's device, its CU count, the grid
-// of a tile-walking kernel, the diagnostic knobs, and launch_fn -- the one path by which these two
-// files start a kernel and report a failure.  Knows nothing of the codec's argument types.
+// Host-only launch layer of the library: the stream's device (Queue), DeviceGuard, cu_count, the
+// grid of a tile-walking kernel, the diagnostic knobs, and launch<kernel> -- the one path by which
+// every translation unit starts a kernel and reports a failure.  Knows no kernel's argument types.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
+#include <utility>
 
 #include "common.h"
 
@@ -64,42 +65,105 @@ inline int64_t grid_for(int64_t ntiles, int lds_bytes, int device) {
   return std::max<int64_t>(1, std::min(g, debug_grid_cap()));
 }
 
-// What launch_fn remembers of one kernel, per device.  Entries are atomics: the first launches on
+// Makes `device` current for a scope, if it is not already, and restores the previous one on exit.
+// status() reports a failed setup; the destructor never fails.
+class DeviceGuard {
+ public:
+  explicit DeviceGuard(int device) {
+    err_ = hipGetDevice(&prev_);
+    if (err_ == hipSuccess && prev_ != device) {
+      err_ = hipSetDevice(device);
+      restore_ = err_ == hipSuccess;
+    }
+  }
+  ~DeviceGuard() {
+    if (restore_) (void)hipSetDevice(prev_);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+  hipError_t status() const { return err_; }
+
+ private:
+  int prev_ = 0;
+  bool restore_ = false;
+  hipError_t err_;
+};
+
+// What launch remembers of one kernel, per device.  Entries are atomics: the first launches on
 // a device may race from several host threads, and every racer stores the same values.
 struct FnCache {
   std::atomic<hipFunction_t> fn[16];
   std::atomic<bool> big_lds[16];   // dynamic LDS above 64 KB has been granted (up to the CU's 160 KB)
 };
+template <auto K>
+FnCache& cache_of() {
+  static FnCache c = {};
+  return c;
+}
+template <class T>
+struct same {
+  using type = T;
+};
 
-// Host launch of a kernel through hipModuleLaunchKernel with a cached function handle: the
-// runtime skips hipLaunchKernel's host-function lookup and the GGL template's argument packing,
-// ≈0.15 us of host time per launch (profiles/r02/launch_host_cost.json).  The handle is the one
-// of the STREAM's device (hipGetFuncBySymbol resolves for the current device, so it is looked up
-// under a guard that makes the stream's device current); the first launch that asks for more
-// than 64 KB of dynamic LDS raises the kernel's limit under the same guard.
-template <class... Args>
-int launch_fn(const void* kernel, FnCache& cache, unsigned grid, unsigned block, unsigned lds, const Queue& q,
-              const char* what, Args... args) {
+// A kernel's function handle on the STREAM's device, cached.  hipGetFuncBySymbol resolves for the
+// current device, so it is looked up under a guard that makes the stream's device current; the
+// first request for more than 64 KB of dynamic LDS raises the kernel's limit under the same guard
+// (the limit only bounds what a launch may ask for).
+inline int function_of(const void* kernel, FnCache& cache, unsigned lds, const Queue& q, const char* what,
+                       hipFunction_t& f) {
   const bool cached = q.dev >= 0 && q.dev < 16;
-  hipFunction_t f = cached ? cache.fn[q.dev].load(std::memory_order_acquire) : nullptr;
+  f = cached ? cache.fn[q.dev].load(std::memory_order_acquire) : nullptr;
   const bool grant = lds > 65536 && !(cached && cache.big_lds[q.dev].load(std::memory_order_acquire));
-  if (f == nullptr || grant) {
-    int cur = 0;
-    BEAST_HIP(hipGetDevice(&cur), what);
-    if (cur != q.dev) BEAST_HIP(hipSetDevice(q.dev), what);
-    hipError_t e = hipGetFuncBySymbol(&f, kernel);
-    if (e == hipSuccess && grant)
-      e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (cur != q.dev) BEAST_HIP(hipSetDevice(cur), what);
-    BEAST_HIP(e, what);
-    if (cached) {
-      cache.fn[q.dev].store(f, std::memory_order_release);
-      if (grant) cache.big_lds[q.dev].store(true, std::memory_order_release);
-    }
+  if (f != nullptr && !grant) return BEAST_OK;
+  const DeviceGuard on(q.dev);
+  BEAST_HIP(on.status(), what);
+  BEAST_HIP(hipGetFuncBySymbol(&f, kernel), what);
+  if (grant) {   // up to the CU's 160 KB, less what the kernel declares statically
+    hipFuncAttributes fa;
+    BEAST_HIP(hipFuncGetAttributes(&fa, kernel), what);
+    BEAST_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024 - (int)fa.sharedSizeBytes), what);
   }
-  void* params[] = {static_cast<void*>(&args)...};
-  BEAST_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, lds, q.s, params, nullptr), what);
+  if (cached) {
+    cache.fn[q.dev].store(f, std::memory_order_release);
+    if (grant) cache.big_lds[q.dev].store(true, std::memory_order_release);
+  }
   return BEAST_OK;
+}
+
+// Host launch of a kernel through hipModuleLaunchKernel with the cached handle: the runtime skips
+// hipLaunchKernel's host-function lookup and the GGL template's argument packing, ≈0.15 us of
+// host time per launch (profiles/r02/launch_host_cost.json).  `args` are exactly the kernel's
+// parameter types P..., so their addresses are what hipModuleLaunchKernel expects.  Returns the
+// launch's own status.
+template <class... P>
+int launch_typed(void (*kernel)(P...), FnCache& cache, dim3 grid, unsigned block, unsigned lds, const Queue& q,
+                 const char* what, typename same<P>::type... args) {
+  hipFunction_t f;
+  BEAST_TRY(function_of(reinterpret_cast<const void*>(kernel), cache, lds, q, what, f));
+  void* params[] = {static_cast<void*>(&args)...};
+  BEAST_HIP(hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, block, 1, 1, lds, q.s, params, nullptr), what);
+  return BEAST_OK;
+}
+
+// launch<k>(grid, block, lds, q, "k", args...): the arguments convert to k's own parameter types
+// at compile time (a wrong count or a type that does not convert is a compile error).
+template <auto K, class... A>
+int launch(dim3 grid, unsigned block, unsigned lds, const Queue& q, const char* what, A&&... a) {
+  return launch_typed(K, cache_of<K>(), grid, block, lds, q, what, std::forward<A>(a)...);
+}
+
+// Workgroups of kernel K a CU of the stream's device holds at once at this block size and dynamic
+// LDS, as launch<K> would start them (the LDS grant included); 0 when the runtime cannot say.
+template <auto K>
+int occupancy(int threads, unsigned lds, const Queue& q) {
+  hipFunction_t f;
+  int per = 0;
+  if (function_of(reinterpret_cast<const void*>(K), cache_of<K>(), lds, q, "occupancy", f) != BEAST_OK) return 0;
+  const DeviceGuard on(q.dev);
+  if (on.status() != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, K, threads, lds) != hipSuccess)
+    return 0;
+  return per;
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -365,18 +366,17 @@ extern "C" int beast_quantile_prepare(const float* x, int64_t rows, int cols, in
     h.gamma[q] = g;
   }
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_quantile_prepare"));
   auto* st = reinterpret_cast<QState*>(ws + w.state);
   auto* nanf = reinterpret_cast<uint32_t*>(ws + w.nan);
   const int ninit = cols * h.n_tg;
-  hipLaunchKernelGGL(k_init, dim3((ninit + 255) / 256), dim3(256), 0, s, st, nanf,
-                     reinterpret_cast<QHeader*>(ws + w.hdr), cols, h);
-  BEAST_LAUNCHED("k_init");
+  BEAST_TRY(launch<k_init>((ninit + 255) / 256, 256, 0, q, "k_init", st, nanf, reinterpret_cast<QHeader*>(ws + w.hdr),
+                           cols, h));
   if (rows > 0) {
     dim3 grid((unsigned)((rows + KT_R - 1) / KT_R), (unsigned)((cols + 31) / 32));
-    hipLaunchKernelGGL(k_keys, grid, dim3(256), 0, s, x, rows, cols, row_stride,
-                       reinterpret_cast<uint32_t*>(ws + w.keys));
-    BEAST_LAUNCHED("k_keys");
+    BEAST_TRY(launch<k_keys>(grid, 256, 0, q, "k_keys", x, rows, cols, row_stride,
+                             reinterpret_cast<uint32_t*>(ws + w.keys)));
   }
   return BEAST_OK;
 }
@@ -396,11 +396,12 @@ extern "C" int beast_quantile_prepare_segments(const void* seg_table, int nseg, 
   const WsLayout w = ws_layout(rows, cols, n_q);
   BEAST_REQUIRE_CODE(ws_bytes >= w.total, BEAST_E_WORKSPACE, "quantile workspace %zu < %zu", ws_bytes, w.total);
   if (rows > 0 && tps > 0) {
+    Queue q;
+    BEAST_TRY(queue_of(stream, q, "beast_quantile_prepare_segments"));
     dim3 grid((unsigned)(tps * nseg), (unsigned)((cols + 31) / 32));
-    hipLaunchKernelGGL(k_keys_seg, grid, dim3(256), 0, beast::as_stream(stream), static_cast<const QSeg*>(seg_table),
-                       nseg, (int)tps, rows, cols,
-                       reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(workspace) + w.keys));
-    BEAST_LAUNCHED("k_keys_seg");
+    BEAST_TRY(launch<k_keys_seg>(grid, 256, 0, q, "k_keys_seg", static_cast<const QSeg*>(seg_table), nseg, (int)tps,
+                                 rows, cols,
+                                 reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(workspace) + w.keys)));
   }
   return BEAST_OK;
 }
@@ -412,18 +413,18 @@ extern "C" int beast_quantile_hist(int pass, int64_t rows, int cols, int n_q, in
                 "beast_quantile_hist: bad args");
   const WsLayout w = ws_layout(rows, cols, n_q);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  hipStream_t s = beast::as_stream(stream);
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_quantile_hist"));
   const int ntg = 2 * n_q;
   BEAST_HIP(hipMemsetAsync(ws + w.hist, 0, sizeof(uint32_t) * beast_quantile_hist_count(pass, cols, n_q, radix_bits),
-                           s), "hist memset");
+                           q.s), "hist memset");
   if (rows > 0) {
     const int64_t chunk = HIST_CHUNK;
     dim3 grid((unsigned)((rows + chunk - 1) / chunk), (unsigned)cols);
     const size_t lds = sizeof(uint32_t) * (hist_stride(pass, radix_bits) / 2) * (pass == 0 ? 1 : ntg);
-    hipLaunchKernelGGL(k_hist, grid, dim3(HIST_THREADS), lds, s, reinterpret_cast<const uint32_t*>(ws + w.keys), rows,
-                       ntg, pass, radix_bits, reinterpret_cast<const QState*>(ws + w.state),
-                       reinterpret_cast<uint32_t*>(ws + w.hist));
-    BEAST_LAUNCHED("k_hist");
+    BEAST_TRY(launch<k_hist>(grid, HIST_THREADS, lds, q, "k_hist", reinterpret_cast<const uint32_t*>(ws + w.keys), rows,
+                             ntg, pass, radix_bits, reinterpret_cast<const QState*>(ws + w.state),
+                             reinterpret_cast<uint32_t*>(ws + w.hist)));
   }
   return BEAST_OK;
 }
@@ -435,11 +436,11 @@ extern "C" int beast_quantile_select(int pass, int cols, int n_q, int radix_bits
   const WsLayout w = ws_layout(0, cols, n_q);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const int n = cols * 2 * n_q;
-  hipLaunchKernelGGL(k_select, dim3(n), dim3(SEL_T), 0, beast::as_stream(stream),
-                     reinterpret_cast<QState*>(ws + w.state), reinterpret_cast<uint32_t*>(ws + w.nan),
-                     reinterpret_cast<const uint32_t*>(ws + w.hist), 2 * n_q, pass, radix_bits, cols);
-  BEAST_LAUNCHED("k_select");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_quantile_select"));
+  return launch<k_select>(n, SEL_T, 0, q, "k_select", reinterpret_cast<QState*>(ws + w.state),
+                          reinterpret_cast<uint32_t*>(ws + w.nan), reinterpret_cast<const uint32_t*>(ws + w.hist),
+                          2 * n_q, pass, radix_bits, cols);
 }
 
 extern "C" int beast_quantile_finalize(int cols, int n_q, void* workspace, float* out, void* stream) {
@@ -447,11 +448,11 @@ extern "C" int beast_quantile_finalize(int cols, int n_q, void* workspace, float
   const WsLayout w = ws_layout(0, cols, n_q);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const int n = cols * n_q;
-  hipLaunchKernelGGL(k_finalize, dim3((n + 127) / 128), dim3(128), 0, beast::as_stream(stream),
-                     reinterpret_cast<const QState*>(ws + w.state), reinterpret_cast<const uint32_t*>(ws + w.nan),
-                     cols, reinterpret_cast<const QHeader*>(ws + w.hdr), out);
-  BEAST_LAUNCHED("k_finalize");
-  return BEAST_OK;
+  Queue q;
+  BEAST_TRY(queue_of(stream, q, "beast_quantile_finalize"));
+  return launch<k_finalize>((n + 127) / 128, 128, 0, q, "k_finalize", reinterpret_cast<const QState*>(ws + w.state),
+                            reinterpret_cast<const uint32_t*>(ws + w.nan), cols,
+                            reinterpret_cast<const QHeader*>(ws + w.hdr), out);
 }
 
 extern "C" int beast_quantile_f32(const float* x, int64_t rows, int cols, int64_t row_stride, int n_q,

@@ -12,6 +12,10 @@
  *   - The caller allocates every input, output and workspace buffer.
  *   - Every call is stream-ordered on `stream` (a hipStream_t passed as void*);
  *     nothing synchronises the device except where a function says so.
+ *   - Every entry point that takes a `stream` works on that stream's device:
+ *     its kernels, their dynamic-LDS grants, the grid sizing (CU count,
+ *     occupancy) and any internal allocation use it.  The caller need not make
+ *     that device current, and its current device is restored on return.
  *   - Return 0 on success or a negative BEAST_E_* code; beast_last_error()
  *     returns a thread-local message for the last failure.  No C++ exception
  *     crosses this boundary.

@@ -165,3 +165,40 @@ def test_tokenizer_on_non_current_device(gpu_device):
             assert torch.equal(a, b)
         else:
             assert a == b
+
+
+@pytest.mark.gpu
+def test_bpe_on_non_current_device(gpu_device):
+    """The BPE kernels on cuda:1 while cuda:0 is current: the encodes that ask for more than 64 KB
+    of LDS, the decode (grid sized by the CU count), train_bpe (its 256-symbol alphabet takes
+    k_count_pairs_lds at 160 KB of LDS) and train_bpe_capi (beast_bpe_train allocates internally)
+    use the stream's device for the LDS grant, the grid and the allocations; every result equals
+    cuda:0's and the current device is still 0.  Needs 2 GPUs, skipped on a one-GPU box."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible GPUs")
+    from beast_tokenizer_amd import BEASTBsplineTokenizer
+    from beast_tokenizer_amd.bpe_codec import GpuBpeModel
+    from beast_tokenizer_amd.bpe_train import fixed_rows_to_device, train_bpe, train_bpe_capi
+    from beast_tokenizer_amd.synthetic import synth_trajectories
+    from test_gpu_bpe_codec import decode_rows, encode_lds_grant_rows, hf_tokenizer, lds_grant_rows
+    torch.cuda.set_device(0)
+    x = torch.from_numpy(synth_trajectories(2048, 50, 14, seed=7))
+    tok = BEASTBsplineTokenizer(num_dof=14, device="cuda:0")
+    tok.fit_parameters([{"actions": x}], verbose=False)
+    corpus = tok.encode(x.to("cuda:0"))[0].cpu()
+    spec, rows = lds_grant_rows(False)
+    res = {}
+    for d in (1, 0):
+        dev = torch.device("cuda", d)
+        got, want = encode_lds_grant_rows(dev)
+        assert got == want
+        dec, counts, status = decode_rows(GpuBpeModel(hf_tokenizer(spec), dev), got["per/rows"], dev, 251)
+        assert dec == rows and not status.any()
+        flat, off = fixed_rows_to_device(corpus.to(dev))
+        py, capi = train_bpe(flat, off, 600), train_bpe_capi(flat, off, 600)
+        torch.cuda.synchronize(dev)
+        assert torch.cuda.current_device() == 0
+        res[d] = (got, dec, counts.tolist(), py.vocab, py.merges, capi.vocab, capi.merges)
+    assert res[1] == res[0]
+    assert res[0][3] == res[0][5] and res[0][4] == res[0][6] and len(res[0][4]) > 0

@@ -309,3 +309,61 @@ def test_words_long_rows_match_hf(width, gpu_device):
     for i in np.flatnonzero(st == 0):
         assert ids[i, :lens[i]].tolist() == want[i]
     assert _lib.load() is not None
+
+
+def lds_grant_rows(narrow):
+    """Eight rows whose encode asks for more than 64 KB of dynamic LDS: golden rows of 140 code
+    points and, unless `narrow`, one of 250 holding more than 384 byte symbols (code points above
+    127 are two), which takes k_bpe_encode's RM_PER instantiation instead of the narrow one."""
+    spec = CODEC["rand256/2048"]
+    rows = sorted((cps for cps, _ in spec["encode"]), key=lambda r: -sum(c >= 128 for c in r))
+    long_row = (rows[0] + rows[1])[:250]
+    assert sum(1 + (c >= 128) for c in long_row) > 384 and 2 * len(long_row) <= 512
+    assert 2 * max(len(r) for r in rows[2:10]) <= 384
+    return spec, rows[2:9] + [rows[9] if narrow else long_row]
+
+
+def encode_lds_grant_rows(dev):
+    """The rows of lds_grant_rows through beast_bpe_encode_rows (k_bpe_encode, RM_PER and narrow)
+    and beast_bpe_encode_rows_words (k_bpe_words), with HF's ids for them: (got, want) by name."""
+    from beast_tokenizer_amd import _lib
+    from beast_tokenizer_amd.bpe_codec import set_encode_path
+    got, want = {}, {}
+    for narrow in (False, True):
+        spec, rows = lds_grant_rows(narrow)
+        tok = hf_tokenizer(spec)
+        model = GpuBpeModel(tok, dev)
+        width = max(len(r) for r in rows)
+        # 16 rows a workgroup at the most: with fewer the launch fills the 160 KB budget to within a row
+        assert 16 * _lib.load().beast_bpe_encode_lds_bytes(width, 2 * width) > 65536
+        assert model._words_ok()
+        hf = [e.ids for e in tok.encode_batch(["".join(map(chr, r)) for r in rows], add_special_tokens=False)]
+        for path in ("rows", "auto"):
+            set_encode_path(path)
+            try:
+                ids, status = encode_rows(model, rows, dev, max_span=255)
+            finally:
+                set_encode_path("auto")
+            assert not status.any()
+            got[f"{'narrow' if narrow else 'per'}/{path}"] = ids
+            want[f"{'narrow' if narrow else 'per'}/{path}"] = hf
+    return got, want
+
+
+def test_encode_lds_grant_in_fresh_process(gpu_device):
+    """The first launch of a BPE encode kernel in a process that asks for more than 64 KB of
+    dynamic LDS: the launch layer raises the kernel's limit itself (no caller sets the attribute),
+    for k_bpe_encode's two instantiations and k_bpe_words alike.  A child process, so that no
+    earlier test has launched these kernels; HF's ids."""
+    import os
+    import subprocess
+    import sys
+    code = ("import torch, test_gpu_bpe_codec as t\n"
+            "got, want = t.encode_lds_grant_rows(torch.device('cuda', 0))\n"
+            "assert sorted(got) == ['narrow/auto', 'narrow/rows', 'per/auto', 'per/rows']\n"
+            "for k in got: assert got[k] == want[k], k\n"
+            "print('ok', sum(len(r) for r in got['per/rows']))\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=os.path.dirname(os.path.abspath(__file__)),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stdout.split()[0] == "ok" and int(r.stdout.split()[1]) > 0
