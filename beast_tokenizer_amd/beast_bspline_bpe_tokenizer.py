@@ -246,6 +246,17 @@ class BEASTBsplineBPETokenizer(BEASTBsplineTokenizer):
         out = (self._discrete_to_bpe(mp_tokens, as_tensors=return_tensors), params)
         return out + (mp_tokens,) if return_mp_tokens else out
 
+    def encode_at(self, trajs: torch.Tensor, times: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                  update_bounds: bool = False, *, return_mp_tokens: bool = False, return_tensors: bool = False,
+                  process_group=None) -> tuple:
+        """``encode`` on per-trajectory time stamps with sample weights
+        (:meth:`BEASTBsplineTokenizer.encode_at`): the BPE ids of those MP tokens."""
+        mp_tokens, params = BEASTBsplineTokenizer.encode_at(self, trajs, times, weights, update_bounds,
+                                                            respect_llm_vocab_size=False,
+                                                            process_group=process_group)
+        out = (self._discrete_to_bpe(mp_tokens, as_tensors=return_tensors), params)
+        return out + (mp_tokens,) if return_mp_tokens else out
+
     def bpe_to_mp_tokens(self, tokens: Iterable[TokenLike]) -> torch.Tensor:
         """Convert BPE tokens back to discrete BEAST bins."""
         return self._bpe_to_discrete(tokens)

@@ -6,6 +6,9 @@ ROCm GPU (MI355X / gfx950):
 
 * ``encode``          -> ``beast_encode_f32``: fit + clamp + quantise + (d t)->(t d)
                          + LLM offset in one kernel (reference :399-428)
+* ``encode_at``       -> ``beast_encode_rows_f32``: the same on per-trajectory time stamps with
+                         sample weights (learn_mp_params_from_trajs with [B, T] times,
+                         mp/uni_bspline.py:471-602); an extension of the surface
 * ``compute_weights`` -> ``beast_encode_f32`` without the quantiser (:344-360)
 * ``decode``          -> ``beast_reconstruct_f32`` dequantise only (:483-496)
 * ``reconstruct_traj``-> ``beast_reconstruct_f32`` (:498-536)
@@ -749,6 +752,102 @@ class BEASTBsplineTokenizer(TokenizerBase):
         tokens = self._quantize(params, 0, p.dev, mode=1)
         params_dict = {"params": params, **self._cond_dict()}
         return tokens, params_dict
+
+    # ===============================================
+    #     - encoding on per-trajectory time grids -
+    # ===============================================
+
+    def _fit_rows(self, trajs, times, weights, tokens_offset: Optional[int]):
+        """One launch of beast_encode_rows_f32 (csrc/fit_rows.hip): the weighted ridge fit of every
+        trajectory on its own time stamps.  Returns (params, tokens or None, device).  The
+        argument checks run before the device is asked for."""
+        if self._basis.conditioned:
+            raise NotImplementedError(
+                "encode_at supports init_cond_order = end_cond_order = 0 only: the conditions come from "
+                "y0, y1 and one dt of the shared grid (uni_bspline.py:499-550), not from per-row times")
+        trajs, times = torch.as_tensor(trajs), torch.as_tensor(times)
+        if trajs.dim() != 3 or times.dim() not in (1, 2) or tuple(times.shape) not in (
+                tuple(trajs.shape[1:2]), tuple(trajs.shape[:2])):
+            # learn_mp_params_from_trajs asserts trajs.shape[:-1] == times.shape (uni_bspline.py:487)
+            raise AssertionError(f"trajectory shape {tuple(trajs.shape)} does not match times {tuple(times.shape)}: "
+                                 "need [B, T, num_dof] with times [B, T] or [T]")
+        B, T, Din = trajs.shape
+        if T < 1:
+            raise ValueError("times must hold at least one point")
+        if weights is not None:
+            weights = torch.as_tensor(weights)
+            if weights.dim() not in (1, 2) or tuple(weights.shape) not in ((T,), (B, T)):
+                raise ValueError(f"weights must be [T] or [B, T]; got {tuple(weights.shape)} for B={B}, T={T}")
+        order = self.joint_indices + self.gripper_indices
+        if order and Din <= max(order):
+            raise IndexError(f"index {max(order)} is out of bounds for dimension 2 with size {Din}")
+        dev = self._dev()
+
+        def rows(x):   # fp32 on dev with unit stride along T; (tensor, batch stride)
+            x = x.to(dev, dtype=torch.float32)
+            if x.stride(-1) != 1 and T > 1:
+                x = x.contiguous()
+            return x, (x.stride(0) if x.dim() == 2 and B > 1 else 0)
+
+        trajs = trajs.to(dev, dtype=torch.float32)
+        times, t_sb = rows(times)
+        w_sb = 0
+        if weights is not None:
+            weights, w_sb = rows(weights)
+        D, N, basis = self.num_dof, self.num_basis, self._basis
+        kj = basis.knots(dev, 0)
+        kg = basis.knots(dev, 1) if basis.has_gripper else None
+        src, _ = self._dof_maps(dev)
+        params = torch.empty((B, D * N), dtype=torch.float32, device=dev)
+        tokens = wmn = wmx = None
+        if tokens_offset is not None:
+            tokens = torch.empty((B, N * D), dtype=torch.int64, device=dev)
+            wmn, wmx = self._bounds(dev)
+        if B == 0:   # an empty tensor has no address to pass
+            return params, tokens, dev
+        st = trajs.stride()
+        _lib.run("beast_encode_rows_f32", trajs.data_ptr(), B, T, st[0], st[1], st[2], D, self.joint_dof,
+                 src.data_ptr(), times.data_ptr(), t_sb, _lib.ptr(weights), w_sb, basis.tau, basis.delay,
+                 kj.data_ptr(), kj.numel(), _lib.ptr(kg), 0 if kg is None else kg.numel(), basis.degrees[0], N,
+                 basis.reg, _lib.ptr(wmn), _lib.ptr(wmx), self.vocab_size, tokens_offset or 0, params.data_ptr(),
+                 _lib.ptr(tokens), _lib.stream_of(dev))
+        return params, tokens, dev
+
+    @torch.no_grad()
+    def encode_at(self, trajs, times, weights=None, update_bounds=False, *, respect_llm_vocab_size=True,
+                  process_group=None):
+        """``encode`` for trajectories on their OWN time stamps: (tokens int64 [B, num_basis*num_dof],
+        {"params": fp32 [B, num_dof*num_basis], ...}) from one launch of ``beast_encode_rows_f32``.
+
+        ``trajs`` [B, T, >= num_dof]; ``times`` [B, T] or [T] (seconds on the tokenizer's
+        [0, duration] axis; T is the trajectory's own length and need not equal ``seq_len``);
+        ``weights`` [B, T], [T] or None (all ones), >= 0.  Every trajectory gets the weighted ridge
+        fit argmin sum_t w_t (y_t - Phi(t_t) p)^2 + reg |p|^2 of
+        UniformBSpline.learn_mp_params_from_trajs (mp/uni_bspline.py:471-602) on its own basis, in
+        float64, rounded once.  A weight of 0 skips the sample: its time and values are never
+        read into the fit and may be NaN (missing frames, padded tails); a trajectory with no
+        weight at all gets params 0.  Negative or non-finite weights are undefined.
+
+        ``update_bounds`` / ``process_group`` / ``respect_llm_vocab_size`` as in ``encode``.
+        Tokenizers with init / end conditions raise ``NotImplementedError``."""
+        offset = self._offset(respect_llm_vocab_size)
+        if update_bounds:
+            params, _, dev = self._fit_rows(trajs, times, weights, None)
+            self.update_weights_bounds_per_batch(params, process_group=process_group)
+            tokens = self._quantize(params, offset, dev, mode=0)
+        else:
+            params, tokens, _ = self._fit_rows(trajs, times, weights, offset)
+        return tokens, {"params": params, **self._cond_dict()}
+
+    @torch.no_grad()
+    def encode_continuous_at(self, trajs, times, weights=None, update_bounds=False, *, process_group=None):
+        """``encode_continuous`` on per-trajectory time stamps: the params of ``encode_at``
+        normalised to [-1, 1] in (t d) order."""
+        params, _, dev = self._fit_rows(trajs, times, weights, None)
+        if update_bounds:
+            self.update_weights_bounds_per_batch(params, process_group=process_group)
+        tokens = self._quantize(params, 0, dev, mode=1)
+        return tokens, {"params": params, **self._cond_dict()}
 
     # ===============================================
     #           - tokenizer LLM tokenization -

@@ -14,38 +14,20 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "basis_device.h"
 #include "common.h"
 #include "launch.h"
 
 namespace {
 
-
 // ------------------------------------------------------------------ basis --
-template <int K>
-__device__ float bfun(int i, float u, const float* __restrict__ kv, int nctrl) {
-  if constexpr (K == 0) {
-    const float a = kv[i], b = kv[i + 1];
-    const bool in = (i == nctrl - 1) ? (u >= a && u <= b) : (u >= a && u < b);
-    return in ? 1.0f : 0.0f;
-  } else {
-    const float d1 = __fsub_rn(kv[i + K], kv[i]);
-    const float d2 = __fsub_rn(kv[i + K + 1], kv[i + 1]);
-    float t1 = 0.0f, t2 = 0.0f;
-    if (!(d1 == 0.0f)) t1 = __fmul_rn(__fdiv_rn(__fsub_rn(u, kv[i]), d1), bfun<K - 1>(i, u, kv, nctrl));
-    if (!(d2 == 0.0f)) t2 = __fmul_rn(__fdiv_rn(__fsub_rn(kv[i + K + 1], u), d2), bfun<K - 1>(i + 1, u, kv, nctrl));
-    return __fadd_rn(t1, t2);
-  }
-}
-
+// bfun<K> and phase_clip: basis_device.h (shared with fit_rows.hip)
 template <int K>
 __global__ void k_basis(const float* __restrict__ times, int64_t n, float tau, float delay,
                         const float* __restrict__ kv, int nctrl, float* __restrict__ out) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  // linear_phase.py:22-24: clip((t - delay) / tau, 0, 1)
-  float u = __fdiv_rn(__fsub_rn(times[i], delay), tau);
-  u = (u < 0.0f) ? 0.0f : u;
-  u = (1.0f < u) ? 1.0f : u;
+  const float u = phase_clip(times[i], tau, delay);
   for (int c = 0; c < nctrl; ++c) out[i * nctrl + c] = bfun<K>(c, u, kv, nctrl);
 }
 
@@ -75,9 +57,7 @@ __global__ void k_basis_deriv(const float* __restrict__ times, int64_t n, float 
                               const float* __restrict__ kv, int nctrl, float* __restrict__ out) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float u = __fdiv_rn(__fsub_rn(times[i], delay), tau);
-  u = (u < 0.0f) ? 0.0f : u;
-  u = (1.0f < u) ? 1.0f : u;
+  const float u = phase_clip(times[i], tau, delay);
   for (int c = 0; c < nctrl; ++c) {
     float v = dbfun<K, R>(c, u, kv, nctrl);
 #pragma unroll

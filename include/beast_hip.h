@@ -160,6 +160,37 @@ int beast_encode_list_f32(const float* const* traj_list, int nbatch, int64_t row
 int beast_quantize_f32(const float* params, int64_t B, int D, int N, const float* w_min, const float* w_max,
                        int vocab, int64_t tok_offset, int mode, int64_t* tokens_out, float* ntok_out, void* stream);
 
+/* Fit + quantise on PER-TRAJECTORY time grids with sample weights, one launch: what
+ * UniformBSpline.learn_mp_params_from_trajs (mp/uni_bspline.py:471-602) computes when its
+ * `times` [*add_dim, T] differ from row to row (init / end condition order 0), extended by a
+ * weight per sample, followed by beast_encode_f32's clamp, quantiser, (d n) -> (n d) and offset.
+ * Per trajectory b and kind (kind 0: the first n_joint DoFs at `degree`; kind 1: the rest at
+ * degree 0), with Phi[t][n] = B_n(clip((times[t] - delay) / tau, 0, 1)), to the bit what
+ * beast_bspline_basis_f32 gives for these times:
+ *   G = Phi^T diag(w) Phi + reg I,  R = Phi^T diag(w) Y,  params = G^-1 R
+ * G, R and the solve (Gauss-Jordan, partial pivoting) are float64; params are rounded to fp32
+ * once.  No shared projection is involved: every trajectory has its own Gram matrix.
+ *   traj[b*sb + t*st + dof_src[d]*sd]  fp32 input, element strides (as beast_encode_f32)
+ *   times       [T] per trajectory, batch stride times_sb (0: one row shared by all)
+ *   weights     nullable (all ones): [T] per trajectory >= 0, batch stride weights_sb (0: shared).
+ *               WEIGHT 0 SKIPS THE SAMPLE: its time and its values are not used at all and may
+ *               be NaN / inf (the mark of a missing frame).  A trajectory whose weights are
+ *               all 0 gets params exactly 0.  Negative or non-finite weights are undefined.
+ *   knots_joint [degree + 1 + N], knots_grip [1 + N]: the two kinds' knot vectors (each
+ *               required only when its kind has DoFs); reg: the ridge term (the reference's 1e-9)
+ *   params_out  [B][D*N] fp32 (d n), nullable; tokens_out [B][N*D] int64 (n d), nullable: bitwise
+ *               beast_quantize_f32 (mode 0) of params_out; needs w_min, w_max, vocab >= 2.
+ * BEAST_E_INVALID: a null required pointer, B < 0, T < 1, N < 1, D < 1, n_joint outside
+ * [0, D], a negative stride, a knot count other than the above.  BEAST_E_UNSUPPORTED outside
+ * beast_encode_f32's envelope: N <= 16, T <= 256, D <= 64, degree <= 8 (any strides). */
+int beast_encode_rows_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st, int64_t sd, int D,
+                          int n_joint, const int32_t* dof_src, const float* times, int64_t times_sb,
+                          const float* weights, int64_t weights_sb, float tau, float delay,
+                          const float* knots_joint, int n_knots_joint, const float* knots_grip,
+                          int n_knots_grip, int degree, int N, double reg, const float* w_min,
+                          const float* w_max, int vocab, int64_t tok_offset, float* params_out,
+                          int64_t* tokens_out, void* stream);
+
 /* ------------------------------------------------------------- H6 - H8 ---
  * Replaces BEASTBsplineTokenizer.decode + reconstruct_traj (beast/
  * beast_bspline_tokenizer.py:483-536) -> discrete_to_continuous (beast/
