@@ -29,6 +29,15 @@ OPT_BPE_ENCODE_MODE = 5
 OPT_BPE_DEDUP_KEY_BITS = 6
 OPT_BPE_TRAIN_HOST_LOOP = 7
 OPT_LAST_CODEC_LAUNCH = 8   # read-only
+# beast_bpe_loop_batch flags, and the int32 words of the loop state a host reads
+BPE_BATCH_INIT = 1
+BPE_BATCH_NO_MERGE = 2
+BPE_BATCH_NO_APPLY = 4
+BPE_STATE_ACTIVE = 0
+BPE_STATE_VCUR = 1
+BPE_STATE_NMERGES = 2
+BPE_STATE_PASSES = 9
+BPE_LOOP_P = 0x9E3779B97F4A7C15   # odd multiplier of the token-string hash (csrc/bpe_vocab.h LOOP_P)
 
 # kernel families of OPT_LAST_CODEC_LAUNCH (bits 0-3), in the header's order
 CODEC_FAMILIES = (None, "encode_v", "encode_spec", "encode_dyn", "reconstruct_v", "reconstruct_spec",

@@ -104,6 +104,22 @@ class GpuBpeOps:
         torch.cuda.current_stream(self.device).synchronize()
         return [int(v) for v in h.tolist()]
 
+    def _upload_luts(self, lut: np.ndarray, byte2id: np.ndarray):
+        lut_d = torch.from_numpy(np.ascontiguousarray(lut)).to(self.device)
+        b2i = torch.from_numpy(np.ascontiguousarray(byte2id, dtype=np.uint16).view(np.int16)).to(self.device)
+        return lut_d, b2i
+
+    def _loop_words(self, sym2, w2, l2, c2, nu: int, nsp: int, **base):
+        """The words dict of a repack's outputs (nu words, nsp padded symbols): the symbols trimmed
+        to their length, plus the words' Bloom signatures -- the layout the merge loop scans."""
+        sym2 = sym2[:max(nsp, 1)].clone()
+        sig = torch.empty(max(nu, 1), dtype=torch.int64, device=self.device)
+        _lib.run("beast_bpe_word_signatures", sym2.data_ptr(), w2.data_ptr(), l2.data_ptr(), nu, sig.data_ptr(),
+                 self.stream)
+        live = int(l2[:nu].sum()) if nu else 0
+        return dict(base, sym=sym2, wstart=w2, wlen=l2, wcount=c2, sig=sig, n_words=nu, n_distinct=nu,
+                    n_syms_distinct=live, n_syms_padded=nsp)
+
     def minmax(self, tokens: torch.Tensor) -> torch.Tensor:
         out = torch.empty(2, dtype=torch.int64, device=self.device)
         _lib.run("beast_i64_minmax", tokens.data_ptr(), tokens.numel(), out.data_ptr(), self.stream)
@@ -123,8 +139,7 @@ class GpuBpeOps:
     def pretokenize(self, tokens, seq_off, mn, lut: np.ndarray, byte2id: np.ndarray):
         dev, s = self.device, self.stream
         S = seq_off.numel() - 1
-        lut_d = torch.from_numpy(np.ascontiguousarray(lut)).to(dev)
-        b2i = torch.from_numpy(np.ascontiguousarray(byte2id, dtype=np.uint16).view(np.int16)).to(dev)
+        lut_d, b2i = self._upload_luts(lut, byte2id)
         wps = torch.empty(S, dtype=torch.int64, device=dev)
         sps = torch.empty(S, dtype=torch.int64, device=dev)
         _lib.run("beast_bpe_pretok_count", tokens.data_ptr(), seq_off.data_ptr(), S, mn, lut_d.data_ptr(),
@@ -157,8 +172,7 @@ class GpuBpeOps:
         if S <= 0 or nt >= 2 ** 32 - 1:
             return None
         lib = _lib.load()
-        lut_d = torch.from_numpy(np.ascontiguousarray(lut)).to(dev)
-        b2i = torch.from_numpy(np.ascontiguousarray(byte2id, dtype=np.uint16).view(np.int16)).to(dev)
+        lut_d, b2i = self._upload_luts(lut, byte2id)
         info = torch.empty(4, dtype=torch.int64, device=dev)
         nbytes = lib.beast_bpe_pretok_dedup_workspace_bytes(nt)
         while True:
@@ -184,13 +198,7 @@ class GpuBpeOps:
                  on.data_ptr(), s)
         nsp = self._read_i64(on, 1)[0]
         del ws, rws
-        sym2 = sym2[:max(nsp, 1)].clone()
-        sig = torch.empty(m, dtype=torch.int64, device=dev)
-        _lib.run("beast_bpe_word_signatures", sym2.data_ptr(), w2.data_ptr(), l2.data_ptr(), nu, sig.data_ptr(), s)
-        live = int(l2[:nu].sum()) if nu else 0
-        words = dict(sym=sym2, wstart=w2, wlen=l2, wcount=c2, sig=sig, n_words=nu, n_distinct=nu,
-                     n_syms=nsp, n_syms_distinct=live, n_syms_padded=nsp)
-        return words, nw, ns
+        return self._loop_words(sym2, w2, l2, c2, nu, nsp, n_syms=nsp), nw, ns
 
     def dedup(self, words):
         """Distinct words of >= 2 symbols x their counts (HF trains on word counts)."""
@@ -228,12 +236,7 @@ class GpuBpeOps:
                  on.data_ptr(), s)
         ns = self._read_i64(on, 1)[0]
         del ws
-        sym2 = sym2[:max(ns, 1)].clone()
-        sig = torch.empty(m, dtype=torch.int64, device=dev)
-        _lib.run("beast_bpe_word_signatures", sym2.data_ptr(), w2.data_ptr(), l2.data_ptr(), nu, sig.data_ptr(), s)
-        live = int(l2[:nu].sum()) if nu else 0
-        return dict(words, sym=sym2, wstart=w2, wlen=l2, wcount=c2, sig=sig, n_words=nu, n_distinct=nu,
-                    n_syms_distinct=live, n_syms_padded=ns)
+        return self._loop_words(sym2, w2, l2, c2, nu, ns, **words)
 
     def gather_words(self, words, gather):
         """Every rank's distinct words x counts on every rank (one all-gather per array),
@@ -313,10 +316,7 @@ class GpuBpeOps:
         return self._deltas
 
     # -- device-driven batched loop (csrc/bpe_loop.hip k_merge_batch + k_apply_batch)
-    LOOP_P = 0x9E3779B97F4A7C15   # odd multiplier of the token-string hash
-    # int32 words of the loop state (csrc/bpe_loop.hip LoopState)
-    ST_ACTIVE, ST_VCUR, ST_NMERGES, ST_PASSES = 0, 1, 2, 9
-    BATCH_INIT, BATCH_NO_MERGE, BATCH_NO_APPLY = 1, 2, 4
+    LOOP_P = _lib.BPE_LOOP_P   # the token-string hash's multiplier (a test overrides it to force collisions)
 
     def loop_kind(self) -> str:
         """'batch' (up to 8 exact merges per pass; 'batch2' / 'batch4' cap a pass at 2 / 4).  An
@@ -337,16 +337,8 @@ class GpuBpeOps:
         lib = _lib.load()
         dev, s = self.device, self.stream
         n_tok = len(id2str)
-        max_merges = 4 * max(vocab_size - n_tok, 0) + 1024
-        P, M = self.LOOP_P, (1 << 64) - 1
-        h0, p0 = np.zeros(n_tok, dtype=np.uint64), np.zeros(n_tok, dtype=np.uint64)
-        for i, t in enumerate(id2str):
-            h, pw = 0, 1
-            for byte in t.encode("utf-8"):
-                h = (h * P + byte) & M
-                pw = (pw * P) & M
-            h0[i], p0[i] = h, pw
-        hp = torch.from_numpy(np.stack([h0, p0]).view(np.int64)).to(dev)
+        max_merges = loop_log_capacity(vocab_size, n_tok)
+        hp = torch.from_numpy(np.stack(token_hashes(id2str, self.LOOP_P)).view(np.int64)).to(dev)
         max_tlen = int(max((len(t) for t in id2str), default=0))
         nb = lib.beast_bpe_loop_workspace_bytes(Vt, max_merges)
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -393,7 +385,7 @@ class GpuBpeOps:
                 ev.record(torch.cuda.current_stream(dev))   # the stream the launches and the copy use
                 inflight.append((ev, bi, steps))
 
-            launch(max(1, min(chunk, -(-(vocab_size - vcur) // kmax))), self.BATCH_INIT)
+            launch(max(1, min(chunk, -(-(vocab_size - vcur) // kmax))), _lib.BPE_BATCH_INIT)
             while True:
                 left = vocab_size - vcur - 4 * sum(p for _, _, p in inflight)
                 if left > 0:
@@ -401,7 +393,7 @@ class GpuBpeOps:
                 ev, bi, _ = inflight.pop(0)
                 ev.synchronize()
                 host.copy_(stage[bi])
-                active, vcur = int(host[self.ST_ACTIVE]), int(host[self.ST_VCUR])
+                active, vcur = int(host[_lib.BPE_STATE_ACTIVE]), int(host[_lib.BPE_STATE_VCUR])
                 if not active or vcur >= vocab_size:
                     break
                 if not inflight:   # the estimate held back: keep one chunk going
@@ -410,23 +402,43 @@ class GpuBpeOps:
         else:
             # sharded: every rank holds the same table and takes the same decisions, so every rank
             # runs the same number of passes (and collectives)
-            run(0, self.BATCH_INIT)
+            run(0, _lib.BPE_BATCH_INIT)
             while True:
                 steps = max(1, min(chunk, (vocab_size - vcur + 1) // 2))
                 for _ in range(steps):
-                    run(1, self.BATCH_NO_APPLY)
+                    run(1, _lib.BPE_BATCH_NO_APPLY)
                     reduce(deltas, "sum")
-                    run(1, self.BATCH_NO_MERGE)
+                    run(1, _lib.BPE_BATCH_NO_MERGE)
                 host.copy_(state[:16], non_blocking=True)
                 torch.cuda.current_stream(dev).synchronize()
-                active, vcur = int(host[self.ST_ACTIVE]), int(host[self.ST_VCUR])
+                active, vcur = int(host[_lib.BPE_STATE_ACTIVE]), int(host[_lib.BPE_STATE_VCUR])
                 if not active or vcur >= vocab_size:
                     break
-        n = int(host[self.ST_NMERGES])
-        self.loop_passes = int(host[self.ST_PASSES])
+        n = int(host[_lib.BPE_STATE_NMERGES])
+        self.loop_passes = int(host[_lib.BPE_STATE_PASSES])
         self.last_apps = apps[:n].cpu().numpy().astype(np.int64) if apps is not None else None
         log = ws[log_off:log_off + 16 * n].view(torch.int32).reshape(n, 4).cpu().numpy() if n else np.zeros((0, 4))
         return [tuple(int(v) for v in r) for r in log], n >= max_merges
+
+
+def loop_log_capacity(vocab_size: int, n_base: int) -> int:
+    """Entries of the device loop's merge log (csrc/bpe_vocab.h loop_log_capacity): a merge that
+    re-uses an id does not grow the vocabulary, so there may be more than vocab_size - n_base."""
+    return 4 * max(vocab_size - n_base, 0) + 1024
+
+
+def token_hashes(id2str: Sequence[str], P: int = _lib.BPE_LOOP_P) -> Tuple[np.ndarray, np.ndarray]:
+    """Per token the polynomial hash of its UTF-8 bytes, h = sum bytes[i] * P^(n-1-i), and P^n
+    (mod 2^64): what the device loop's string table starts from (csrc/bpe_vocab.h token_hashes)."""
+    M = (1 << 64) - 1
+    h0, p0 = np.zeros(len(id2str), dtype=np.uint64), np.zeros(len(id2str), dtype=np.uint64)
+    for i, t in enumerate(id2str):
+        h, pw = 0, 1
+        for byte in t.encode("utf-8"):
+            h = (h * P + byte) & M
+            pw = (pw * P) & M
+        h0[i], p0[i] = h, pw
+    return h0, p0
 
 
 def replay_log(id2str: List[str], str2id: Dict[str, int], log) -> Optional[List[Tuple[str, str]]]:

@@ -13,8 +13,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 
 #include "bpe_common.h"
+#include "bpe_vocab.h"
 #include "common.h"
 #include "launch.h"
 
@@ -472,6 +474,11 @@ struct LoopState {
   uint32_t blen[BK];
   unsigned long long bh[BK];
 };
+// the words a host reads through beast_bpe_loop_state (include/beast_hip.h)
+static_assert(offsetof(LoopState, active) == 4 * BEAST_BPE_STATE_ACTIVE, "BEAST_BPE_STATE_ACTIVE");
+static_assert(offsetof(LoopState, vcur) == 4 * BEAST_BPE_STATE_VCUR, "BEAST_BPE_STATE_VCUR");
+static_assert(offsetof(LoopState, n_merges) == 4 * BEAST_BPE_STATE_NMERGES, "BEAST_BPE_STATE_NMERGES");
+static_assert(offsetof(LoopState, passes) == 4 * BEAST_BPE_STATE_PASSES, "BEAST_BPE_STATE_PASSES");
 
 // Token strings are identified by (64-bit polynomial hash of their UTF-8 bytes, byte length):
 // h(xy) = h(x) * P^len(y) + h(y), so a merge's string is hashed from its parts.  The table maps
@@ -493,7 +500,7 @@ __device__ __forceinline__ unsigned long long lid_of(uint32_t len, int id) {
 }
 
 __device__ __forceinline__ uint64_t loop_slot(unsigned long long h, uint32_t len, int log2cap) {
-  return ((h ^ ((unsigned long long)len * 0x9E3779B97F4A7C15ull)) * 0xbf58476d1ce4e5b9ull) >> (64 - log2cap);
+  return ((h ^ ((unsigned long long)len * beast::bpe::LOOP_P)) * 0xbf58476d1ce4e5b9ull) >> (64 - log2cap);
 }
 
 constexpr int KR = 4;   // candidate pairs per table row: its KR best, in HF order

@@ -413,6 +413,12 @@ int beast_bpe_loop_state(const void* ws, int Vt, int max_merges, const void** st
 #define BEAST_BPE_BATCH_INIT 1
 #define BEAST_BPE_BATCH_NO_MERGE 2
 #define BEAST_BPE_BATCH_NO_APPLY 4
+/* The int32 words of the state (beast_bpe_loop_state) a host reads, of its first 16: the loop
+ * still runs; the vocabulary size; the merges logged; the passes decided. */
+#define BEAST_BPE_STATE_ACTIVE 0
+#define BEAST_BPE_STATE_VCUR 1
+#define BEAST_BPE_STATE_NMERGES 2
+#define BEAST_BPE_STATE_PASSES 9
 size_t beast_bpe_batch_workspace_bytes(int Vt);
 size_t beast_bpe_batch_delta_count(int Vt);
 int beast_bpe_loop_batch(void* ws, int Vt, int max_merges, int n_steps, int max_batch, int flags, uint16_t* sym,

@@ -181,6 +181,18 @@ def test_option_constants_match_header():
     assert defs["LAST_CODEC_LAUNCH"] == 8
 
 
+def test_bpe_loop_constants_match_header():
+    """Every BEAST_BPE_BATCH_* / BEAST_BPE_STATE_* of include/beast_hip.h has the same value as
+    _lib.BPE_BATCH_* / _lib.BPE_STATE_*, and vice versa (csrc/bpe_loop.hip pins the state's words
+    to its struct with static_asserts)."""
+    defs = {m.group(1): int(m.group(2))
+            for m in re.finditer(r"#define BEAST_BPE_((?:BATCH|STATE)_\w+) (\d+)", open(HEADER).read())}
+    consts = {k[4:]: v for k, v in vars(_lib).items() if k.startswith(("BPE_BATCH_", "BPE_STATE_"))}
+    assert defs == consts
+    assert defs == {"BATCH_INIT": 1, "BATCH_NO_MERGE": 2, "BATCH_NO_APPLY": 4,
+                    "STATE_ACTIVE": 0, "STATE_VCUR": 1, "STATE_NMERGES": 2, "STATE_PASSES": 9}
+
+
 def test_last_codec_launch_is_read_only_and_zero_before_any_launch():
     """BEAST_OPT_LAST_CODEC_LAUNCH reads 0 in a process that has launched nothing (a fresh one: this
     process may have run GPU tests), decodes to an empty record, and beast_set_option refuses it."""
