@@ -68,6 +68,8 @@ SIGNATURES = {
                                      _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "beast_reconstruct_derivs_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp,
                                             _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "beast_reconstruct_derivs_bwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32,
+                                                _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "beast_roundtrip_stats_f32": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
                                          _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "beast_colminmax_workspace_bytes": (_sz, [_i64, _i32]),

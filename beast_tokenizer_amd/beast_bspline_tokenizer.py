@@ -39,6 +39,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .base_tokenizer import TokenizerBase
@@ -172,6 +173,53 @@ class _Plan:
     def cacheable(self) -> bool:
         # bounds living elsewhere were copied to the device: do not reuse the copy
         return self.keep[4] is self.wmin and self.keep[5] is self.wmax
+
+
+class _ReconstructContinuous(torch.autograd.Function):
+    """``reconstruct_traj_continuous`` (``orders`` None) / ``reconstruct_traj_continuous_derivs``
+    with a backward.  The forward is the launch those methods always made; the backward is one
+    launch of ``beast_reconstruct_derivs_bwd_f32`` over the slabs the forward used.  ``params`` is
+    contiguous fp32 [B, N*D] on the plan's device, ``init_p`` what ``_init_p_rows`` returns."""
+
+    @staticmethod
+    def forward(ctx, params, init_p, tok, p, times, orders):
+        B = params.shape[0]
+        if orders is None:   # beast_reconstruct_f32: its [2][T][N] basis is order 0's slab
+            basis = tok._basis_for(times, B, p)
+            outs = (tok._reconstruct(None, params, times, init_p, False, p, basis),)
+            keep, p_basis, basis_sb, slots = basis[0], basis[1], basis[2], (0,)
+        else:
+            basis = tok._deriv_basis_for(times, B, p, orders)
+            outs = tok._reconstruct_derivs(None, params, times, orders, init_p, False, p, basis)
+            keep, p_basis, basis_sb, slots = basis[0], basis[0].data_ptr(), basis[1], orders
+        ctx.set_materialize_grads(False)       # an unused output's gradient stays None: a null pointer
+        ctx.save_for_backward(params)
+        # keep and p own the memory behind p_basis and the plan's pointers
+        ctx.state = (tok, p, keep, p_basis, basis_sb, outs[0].shape[1], slots,
+                     None if init_p is None else tuple(init_p.shape))
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        (params,) = ctx.saved_tensors
+        tok, p, _, p_basis, basis_sb, Tn, slots, ip_shape = ctx.state
+        none = (None,) * 6
+        if all(g is None for g in grads):
+            return none
+        g3 = [None, None, None]
+        for o, g in zip(slots, grads):
+            if g is not None:   # y.sum().backward() delivers a stride-0 expansion: the kernel needs rows
+                g3[o] = g.to(device=p.dev, dtype=torch.float32).contiguous()
+        grad_params = torch.empty_like(params)
+        grad_ip = None
+        if ip_shape is not None and ctx.needs_input_grad[1]:
+            grad_ip = torch.zeros(ip_shape, dtype=torch.float32, device=p.dev)
+        _lib.run("beast_reconstruct_derivs_bwd_f32", *map(_lib.ptr, g3), params.shape[0], tok.num_dof, tok.joint_dof,
+                 tok.num_basis, p.p_wmn, p.p_wmx, p_basis, basis_sb, Tn, p.p_dst, tok.num_dof, params.data_ptr(),
+                 None if ip_shape is None else p.p_dst, grad_params.data_ptr(), _lib.ptr(grad_ip),
+                 0 if ip_shape is None else ip_shape[1], _lib.raw_stream(p.idx))
+        return (grad_params if ctx.needs_input_grad[0] else None, grad_ip) + none[2:]
 
 
 class BEASTBsplineTokenizer(TokenizerBase):
@@ -927,19 +975,24 @@ class BEASTBsplineTokenizer(TokenizerBase):
         phi[:, : self._basis.n_kinds] = phi_k.permute(1, 0, 2, 3)
         return phi, phi.data_ptr(), 2 * Tn * N, Tn
 
-    def _reconstruct(self, tokens, ntokens, times, init_p, respect_llm_vocab_size, p: _Plan):
+    def _init_p_rows(self, init_p, B: int, p: _Plan):
+        """init_p as the kernels read it (fp32 rows on the plan's device, unit column stride), or
+        None where the reconstruction does not use it."""
+        if init_p is None or not self.init_pos or self.joint_dof == 0:
+            return None
+        ip = torch.as_tensor(init_p).to(p.dev, dtype=torch.float32)
+        if ip.dim() != 2 or ip.shape[0] != B:
+            raise ValueError(f"init_p must be [B, num_dof]; got {tuple(ip.shape)}")
+        return ip if ip.stride(1) == 1 else ip.contiguous()
+
+    def _reconstruct(self, tokens, ntokens, times, init_p, respect_llm_vocab_size, p: _Plan, basis=None):
         src = tokens if tokens is not None else ntokens
         B = src.shape[0]
         D = self.num_dof
-        phi, p_phi, basis_sb, Tn = self._basis_for(times, B, p)
+        phi, p_phi, basis_sb, Tn = basis or self._basis_for(times, B, p)
         pos = torch.empty((B, Tn, D), dtype=torch.float32, device=p.dev)
-        ip, ip_sb, ip_src = None, 0, None
-        if init_p is not None and self.init_pos and self.joint_dof > 0:
-            ip = torch.as_tensor(init_p).to(p.dev, dtype=torch.float32)
-            if ip.dim() != 2 or ip.shape[0] != B:
-                raise ValueError(f"init_p must be [B, num_dof]; got {tuple(ip.shape)}")
-            if ip.stride(1) != 1:
-                ip = ip.contiguous()
+        ip, ip_sb, ip_src = self._init_p_rows(init_p, B, p), 0, None
+        if ip is not None:
             ip_sb, ip_src = ip.stride(0), p.p_dst      # joint DoFs come first in the dof map
         offset = self._offset(respect_llm_vocab_size) if tokens is not None else 0
         rc = p.rec(None if tokens is None else tokens.data_ptr(), B, D, self.joint_dof, self.num_basis,
@@ -962,19 +1015,33 @@ class BEASTBsplineTokenizer(TokenizerBase):
         tokens = self._token_rows(tokens, p.dev)
         return self._reconstruct(tokens, None, times, kwargs.get("init_p"), True, p)
 
-    @torch.no_grad()
+    @staticmethod
+    def _wants_grad(params, init_p) -> bool:
+        return torch.is_grad_enabled() and (params.requires_grad
+                                            or (isinstance(init_p, torch.Tensor) and init_p.requires_grad))
+
     def reconstruct_traj_continuous(self, params, times=None, **kwargs):
-        """Positions from normalised params in (t d) order (reference :538-582)."""
+        """Positions from normalised params in (t d) order (reference :538-582).
+
+        Differentiable in ``params`` and a tensor ``init_p`` when one of them requires grad (one
+        launch of ``beast_reconstruct_derivs_bwd_f32`` in the backward); any other
+        call records no graph, as the reference's ``no_grad``."""
         p = self._plan()
-        params = params.to(p.dev)
-        if len(params.shape) == 3:
-            params = params.reshape(params.shape[0], -1)
-        if params.shape[-1] != self.num_basis * self.num_dof:
-            raise ValueError(
-                f"Token dimension {params.shape[-1]} does not match expected {self.num_basis * self.num_dof}."
-            )
-        params = params.to(torch.float32).contiguous()
-        return self._reconstruct(None, params, times, kwargs.get("init_p"), False, p)
+        init_p = kwargs.get("init_p")
+        grad = self._wants_grad(params, init_p)
+        with torch.set_grad_enabled(grad):      # the move, reshape and cast carry the gradient back
+            params = params.to(p.dev)
+            if len(params.shape) == 3:
+                params = params.reshape(params.shape[0], -1)
+            if params.shape[-1] != self.num_basis * self.num_dof:
+                raise ValueError(
+                    f"Token dimension {params.shape[-1]} does not match expected {self.num_basis * self.num_dof}."
+                )
+            params = params.to(torch.float32).contiguous()
+            if grad:
+                ip = self._init_p_rows(init_p, params.shape[0], p)
+                return _ReconstructContinuous.apply(params, ip, self, p, times, None)[0]
+            return self._reconstruct(None, params, times, init_p, False, p)
 
     # ===============================================
     #     - decoding to velocity / acceleration -
@@ -1017,11 +1084,12 @@ class BEASTBsplineTokenizer(TokenizerBase):
             slabs[:, o, :kinds] = self._basis.deriv_basis_at(t, o).permute(1, 0, 2, 3)   # [kinds, B, T, N]
         return slabs, 3 * 2 * Tn * N, Tn
 
-    def _reconstruct_derivs(self, tokens, ntokens, times, orders, init_p, respect_llm_vocab_size, p: _Plan):
+    def _reconstruct_derivs(self, tokens, ntokens, times, orders, init_p, respect_llm_vocab_size, p: _Plan,
+                            basis=None):
         orders = self._check_orders(orders)
         src = tokens if tokens is not None else ntokens
         B, D = src.shape[0], self.num_dof
-        slabs, basis_sb, Tn = self._deriv_basis_for(times, B, p, orders)
+        slabs, basis_sb, Tn = basis or self._deriv_basis_for(times, B, p, orders)
         if Tn < 1:
             raise ValueError("times must hold at least one point")
         outs = [None, None, None]
@@ -1029,13 +1097,8 @@ class BEASTBsplineTokenizer(TokenizerBase):
             outs[o] = torch.empty((B, Tn, D), dtype=torch.float32, device=p.dev)
         if B == 0:
             return tuple(outs[o] for o in orders)
-        ip, ip_sb, ip_src = None, 0, None
-        if init_p is not None and self.init_pos and self.joint_dof > 0:
-            ip = torch.as_tensor(init_p).to(p.dev, dtype=torch.float32)
-            if ip.dim() != 2 or ip.shape[0] != B:
-                raise ValueError(f"init_p must be [B, num_dof]; got {tuple(ip.shape)}")
-            if ip.stride(1) != 1:
-                ip = ip.contiguous()
+        ip, ip_sb, ip_src = self._init_p_rows(init_p, B, p), 0, None
+        if ip is not None:
             ip_sb, ip_src = ip.stride(0), p.p_dst      # joint DoFs come first in the dof map
         offset = self._offset(respect_llm_vocab_size) if tokens is not None else 0
         _lib.run("beast_reconstruct_derivs_f32", _lib.ptr(tokens), B, D, self.joint_dof, self.num_basis,
@@ -1073,21 +1136,27 @@ class BEASTBsplineTokenizer(TokenizerBase):
         """Accelerations [B, T, num_dof]: ``reconstruct_traj_derivs(..., orders=(2,))[0]``."""
         return self.reconstruct_traj_derivs(tokens, times, (2,), **kwargs)[0]
 
-    @torch.no_grad()
     def reconstruct_traj_continuous_derivs(self, params, times=None, orders=(0, 1, 2), **kwargs):
         """``reconstruct_traj_derivs`` from normalised params in (t d) order (the
-        ``reconstruct_traj_continuous`` input); kwargs: init_p [B, num_dof]."""
+        ``reconstruct_traj_continuous`` input); kwargs: init_p [B, num_dof].  Differentiable as
+        ``reconstruct_traj_continuous`` is: every requested order feeds the one backward launch."""
         orders = self._check_orders(orders)
         p = self._plan()
-        params = params.to(p.dev)
-        if len(params.shape) == 3:
-            params = params.reshape(params.shape[0], -1)
-        if params.dim() != 2 or params.shape[-1] != self.num_basis * self.num_dof:
-            raise ValueError(
-                f"Token dimension {params.shape[-1]} does not match expected {self.num_basis * self.num_dof}."
-            )
-        params = params.to(torch.float32).contiguous()
-        return self._reconstruct_derivs(None, params, times, orders, kwargs.get("init_p"), False, p)
+        init_p = kwargs.get("init_p")
+        grad = self._wants_grad(params, init_p)
+        with torch.set_grad_enabled(grad):
+            params = params.to(p.dev)
+            if len(params.shape) == 3:
+                params = params.reshape(params.shape[0], -1)
+            if params.dim() != 2 or params.shape[-1] != self.num_basis * self.num_dof:
+                raise ValueError(
+                    f"Token dimension {params.shape[-1]} does not match expected {self.num_basis * self.num_dof}."
+                )
+            params = params.to(torch.float32).contiguous()
+            if grad:
+                ip = self._init_p_rows(init_p, params.shape[0], p)
+                return _ReconstructContinuous.apply(params, ip, self, p, times, orders)
+            return self._reconstruct_derivs(None, params, times, orders, init_p, False, p)
 
     # ===============================================
     #           - tokenizer evaluation -

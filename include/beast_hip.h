@@ -237,6 +237,41 @@ int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, int D, int n_
                                  float* pos_out, float* vel_out, float* acc_out, const float* ntokens,
                                  void* stream);
 
+/* The adjoint of beast_reconstruct_derivs_f32 on its ntokens path, in ONE launch: upstream
+ * gradients of the positions, velocities and accelerations -> the gradient of the normalised
+ * tokens (and of init_p).  B .. num_dof_out, basis_sb and init_p_src mean what they mean in the
+ * forward.  With k = d*N + n, kind(d) = 0 for d < n_joint else 1, o over the non-null gradients
+ * (gripper DoFs: o = 0 only) and x = ntokens[b][n*D+d]:
+ *   S[b][d][n]              = sum_t sum_o basis_o[kind(d)][t][n] * grad_o[b][t][dof_dst[d]]
+ *   grad_ntokens[b][n*D+d]  = (-1 <= x <= 1) ? S[b][d][n] * s[k] : 0,   s[k] = 0.5f * (w_max[k] - w_min[k])
+ * s is the exact derivative of denormalize_tensor; both ends of the clamp pass, as in torch's
+ * clamp backward; the mask is a select, so an x outside the range or NaN gives exactly 0 even
+ * where S is not finite.
+ *   grad_pos, grad_vel, grad_acc   [B][T_out][num_dof_out] fp32, contiguous; nullable, at least
+ *               one given.  Columns dof_dst does not name contribute nothing.
+ *   basis       the forward's slabs [3][2][T_out][N]; the slab of a null gradient is never read.
+ *               For beast_reconstruct_f32's [2][T_out][N] basis pass it with grad_pos alone.
+ *   ntokens     [B][N*D]: the forward's input (the clamp mask)
+ *   init_p_src  nullable; non-null means the forward ran with init_p: grad_ntokens is 0 for
+ *               coefficient 0 of the joint DoFs (the forward overwrote it), and
+ *   grad_init_p nullable (needs init_p_src) [B] rows of stride grad_init_p_sb, zero-filled by the
+ *               caller: grad_init_p[b][init_p_src[d]] = S[b][d][0] for d < n_joint; no other
+ *               column is written.
+ *   grad_ntokens  required [B][N*D] (n d), every element written
+ * No atomics: every S is one fma chain over t ascending and, inside each t, o ascending,
+ * whatever B, the tile or the launch variant, so two runs agree bitwise and a row's gradient
+ * does not depend on the batch around it.  Each gradient is read once (16-byte loads where the
+ * three pointers and T_out*num_dof_out allow them).  Same envelope as the forward:
+ * N <= 16, D <= 64, T_out <= 4096, num_dof_out <= 4096, else BEAST_E_UNSUPPORTED. */
+int beast_reconstruct_derivs_bwd_f32(const float* grad_pos, const float* grad_vel, const float* grad_acc,
+                                     int64_t B, int D, int n_joint, int N,
+                                     const float* w_min, const float* w_max,
+                                     const float* basis, int64_t basis_sb, int T_out,
+                                     const int32_t* dof_dst, int num_dof_out,
+                                     const float* ntokens, const int32_t* init_p_src,
+                                     float* grad_ntokens, float* grad_init_p, int64_t grad_init_p_sb,
+                                     void* stream);
+
 /* Error statistics of encode -> reconstruct in ONE launch: how well the tokenizer represents the
  * trajectories, and whether the spline fit or the quantiser is to blame.  traj .. dof_src, proj,
  * N, w_min, w_max, vocab and tok_offset mean what they mean in beast_encode_f32; basis is
