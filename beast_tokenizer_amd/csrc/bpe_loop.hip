@@ -1212,9 +1212,7 @@ __global__ __launch_bounds__(64 * APPLY_ROWS) void k_apply_batch(uint32_t* __res
 #else
       if (full || !row_top_update(row, pre_F, pre_k, x, Vt, lane, n, A, B, N, rt)) rank_row_top(row, x, Vt, vcur, lane, rt);
 #endif
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      beast::wave_sync();
       if (lane < RT_K || lane == RT_F) g[lane] = rt[lane];
       if (lane == 0) aw.clean[x] = 1u;
 #ifdef BPE_MERGE_STAMPS

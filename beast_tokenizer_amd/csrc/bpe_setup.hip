@@ -23,7 +23,8 @@
 
 namespace {
 
-[[maybe_unused]] constexpr int CLS_OTHER = 0, CLS_LETTER = 1, CLS_NUMBER = 2, CLS_WS = 3;
+using beast_pt::CLS_OTHER;
+using beast_pt::CLS_WS;
 
 // ------------------------------------------------------------- min / max --
 __global__ void k_minmax(const long long* __restrict__ x, int64_t n, long long* __restrict__ out) {
@@ -70,22 +71,10 @@ __global__ void k_presence(const long long* __restrict__ x, int64_t n, long long
 }
 
 // ---------------------------------------------------------- pre-tokenise --
-__device__ __forceinline__ int cls_of(long long cp, const uint8_t* __restrict__ lut, int64_t lut_n) {
-  return (cp >= 0 && cp < lut_n) ? lut[cp] : CLS_OTHER;
-}
-
-__device__ __forceinline__ int utf8_len(long long cp) { return cp < 0x80 ? 1 : cp < 0x800 ? 2 : cp < 0x10000 ? 3 : 4; }
-
-__device__ __forceinline__ void utf8_bytes(long long cp, uint8_t* b) {
-  if (cp < 0x80) { b[0] = (uint8_t)cp; }
-  else if (cp < 0x800) { b[0] = (uint8_t)(0xC0 | (cp >> 6)); b[1] = (uint8_t)(0x80 | (cp & 0x3F)); }
-  else if (cp < 0x10000) {
-    b[0] = (uint8_t)(0xE0 | (cp >> 12)); b[1] = (uint8_t)(0x80 | ((cp >> 6) & 0x3F)); b[2] = (uint8_t)(0x80 | (cp & 0x3F));
-  } else {
-    b[0] = (uint8_t)(0xF0 | (cp >> 18)); b[1] = (uint8_t)(0x80 | ((cp >> 12) & 0x3F));
-    b[2] = (uint8_t)(0x80 | ((cp >> 6) & 0x3F)); b[3] = (uint8_t)(0x80 | (cp & 0x3F));
-  }
-}
+using beast_pt::class_global;
+using beast_pt::emit_utf8_ids;
+using beast_pt::utf8_len;
+using beast_pt::wave_sync;
 
 // Length of the GPT-2 contraction ('s|'t|'re|'ve|'m|'ll|'d) starting at s[i] == '\'', or 0.
 __device__ __forceinline__ int contraction(const long long* __restrict__ s, int64_t i, int64_t n, long long mn) {
@@ -115,22 +104,22 @@ __device__ void pretok_serial(const long long* __restrict__ tok, const int64_t* 
   while (i < n) {
     const long long c = s[i] - mn;
     int64_t j;
-    int k = cls_of(c, lut, lut_n);
+    int k = class_global(c, lut, lut_n);
     const int con = (c == '\'') ? contraction(s, i, n, mn) : 0;
     if (con) {
       j = i + con;
     } else {
       int64_t st = i;
       if (c == ' ' && i + 1 < n) {
-        const int k1 = cls_of(s[i + 1] - mn, lut, lut_n);
+        const int k1 = class_global(s[i + 1] - mn, lut, lut_n);
         if (k1 != CLS_WS) { k = k1; st = i + 1; }
       }
       if (k != CLS_WS) {
         j = st + 1;
-        while (j < n && cls_of(s[j] - mn, lut, lut_n) == k) ++j;
+        while (j < n && class_global(s[j] - mn, lut, lut_n) == k) ++j;
       } else {
         j = i + 1;
-        while (j < n && cls_of(s[j] - mn, lut, lut_n) == CLS_WS) ++j;
+        while (j < n && class_global(s[j] - mn, lut, lut_n) == CLS_WS) ++j;
         if (j < n && j - i >= 2) --j;  // \s+(?!\S): leave the last blank for the next word
       }
     }
@@ -141,13 +130,7 @@ __device__ void pretok_serial(const long long* __restrict__ tok, const int64_t* 
       wstart[wo + nw] = (uint32_t)(so + ns);
       wlen[wo + nw] = (uint32_t)wsyms;
       int64_t o = so + ns;
-      for (int64_t p = i; p < j; ++p) {
-        uint8_t b[4];
-        const long long cp = s[p] - mn;
-        const int L = utf8_len(cp);
-        utf8_bytes(cp, b);
-        for (int q = 0; q < L; ++q) sym[o++] = byte2id[b[q]];
-      }
+      for (int64_t p = i; p < j; ++p) o += emit_utf8_ids(s[p] - mn, byte2id, sym + o);
     }
     ns += wsyms;
     ++nw;
@@ -181,10 +164,30 @@ struct PtLdsT {
 };
 using PtLds = PtLdsT<PT_LC>;
 
-__device__ __forceinline__ void pt_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+// One training row (row[0 .. n), n <= LC) into the wave's LDS image, all by csrc/pretok.h: 1. code
+// points, classes, UTF-8 symbol offsets (stage_row: every load of the row is issued before the
+// first is used; round 3 waited per 64-code-point chunk, then for its class from the global LUT);
+// 2. the end of the word that starts at every position (regex_ends, pretok_serial's rules; wcp is
+// its scratch until word_starts); 3. the word chain 0 -> e[0] -> ... walked lane-parallel
+// (word_starts).  bad: the caller's reasons not to take the row; a code point outside [0, 2^31)
+// is another.  Returns the row's byte symbols (L.nw: its words), or -1 (wave-uniform): not taken.
+template <int LC>
+__device__ __forceinline__ int pt_pretok_row(PtLdsT<LC>& L, const long long* __restrict__ row, int n, bool bad,
+                                             int lane, long long mn, const uint8_t* s_lut,
+                                             const uint8_t* __restrict__ lut, int64_t lut_n) {
+  __builtin_assume(n <= LC);
+  const int nsym = beast_pt::stage_row<LC / 64>(row, n, lane, L.so, [&](int i, long long t) {
+    const long long c = t - mn;
+    bad |= (c < 0) | (c > 0x7FFFFFFFLL);
+    L.cp[i] = (int32_t)c;
+    L.cls[i] = (uint8_t)beast_pt::class_of(c, s_lut, lut, lut_n);
+    return utf8_len(c);
+  });
+  if (__any(bad)) return -1;
+  wave_sync();
+  beast_pt::regex_ends(L.cp, L.cls, L.wcp, L.e, n, lane);
+  beast_pt::word_starts(L.e, L.vis, L.wcp, nullptr, &L.nw, n, lane);
+  return nsym;
 }
 
 template <bool EMIT>
@@ -197,50 +200,20 @@ __global__ __launch_bounds__(64 * PT_WAVES) void k_pretok_wave(
   __shared__ PtLds lds[PT_WAVES];
   __shared__ uint8_t s_lut[256];   // classes of code points < 256 (every BEAST bin of a 256 vocab)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lut[i] = i < lut_n ? lut[i] : (uint8_t)CLS_OTHER;
+  beast_pt::stage_lut256(s_lut, lut, lut_n);
   __syncthreads();
   PtLds& L = lds[wv];
-  constexpr int PF = PT_LC / 64;
   for (int64_t sidx = (int64_t)blockIdx.x * PT_WAVES + wv; sidx < n_seq; sidx += (int64_t)gridDim.x * PT_WAVES) {
     const int64_t r0 = seq_off[sidx], n64 = seq_off[sidx + 1] - r0;
-    bool serial = n64 > PT_LC;
+    const bool serial = n64 > PT_LC;
     const int n = serial ? 0 : (int)n64;
-    // 1. code points and classes, then the UTF-8 symbol offsets.  Every load of the row is issued
-    //    before the first is used (round 3 waited for each 64-code-point chunk, then for its class
-    //    from the global LUT: two dependent round trips per chunk)
-    long long tv[PF];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) tv[k] = (lane + 64 * k < n) ? tok[r0 + lane + 64 * k] : 0;
-    int carry = 0;
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-      if (64 * k >= n) break;
-      const int i = 64 * k + lane;
-      int len = 0;
-      if (i < n) {
-        const long long c = tv[k] - mn;
-        serial |= (c < 0) | (c > 0x7FFFFFFFLL);
-        L.cp[i] = (int32_t)c;
-        L.cls[i] = (c >= 0 && c < 256) ? s_lut[c] : (c >= 0 && c < lut_n) ? lut[c] : (uint8_t)CLS_OTHER;
-        len = utf8_len(c);
-      }
-      int tot;
-      const int ex = beast_pt::wave_excl_scan(len, lane, tot);
-      if (i < n) L.so[i] = (int16_t)(carry + ex);
-      carry += tot;
-    }
-    if (__any(serial)) {   // wave-uniform
+    const int carry = pt_pretok_row(L, tok + r0, n, serial, lane, mn, s_lut, lut, lut_n);   // steps 1-3
+    if (carry < 0) {   // wave-uniform
       if (lane == 0)
         pretok_serial<EMIT>(tok, seq_off, sidx, mn, lut, lut_n, words_per_seq, syms_per_seq, word_off, sym_off,
                             byte2id, sym, wstart, wlen);
       continue;
     }
-    if (lane == 0) L.so[n] = (int16_t)carry;
-    pt_wave_sync();
-    // 2. the end of the word that starts at every position (pretok_serial's rules), 3. the word
-    //    chain 0 -> e[0] -> ... walked lane-parallel (csrc/pretok.h; round 3 walked it on lane 0)
-    beast_pt::regex_ends(L.cp, L.cls, L.wcp, L.e, n, lane);   // wcp: scratch until word_starts
-    beast_pt::word_starts(L.e, L.vis, L.wcp, nullptr, &L.nw, n, lane);
     const int nw = L.nw;
     if (!EMIT) {
       if (lane == 0) {
@@ -255,16 +228,9 @@ __global__ __launch_bounds__(64 * PT_WAVES) void k_pretok_wave(
         wstart[wo + w] = (uint32_t)(so0 + s0);
         wlen[wo + w] = (uint32_t)(s1 - s0);
       }
-      for (int i = lane; i < n; i += 64) {
-        uint8_t b[4];
-        const long long cp = L.cp[i];
-        const int Lb = utf8_len(cp);
-        utf8_bytes(cp, b);
-        uint16_t* o = sym + so0 + L.so[i];
-        for (int q = 0; q < Lb; ++q) o[q] = byte2id[b[q]];
-      }
+      for (int i = lane; i < n; i += 64) emit_utf8_ids((long long)L.cp[i], byte2id, sym + so0 + L.so[i]);
     }
-    pt_wave_sync();   // LDS is reused by the next sequence
+    wave_sync();   // LDS is reused by the next sequence
   }
 }
 
@@ -570,7 +536,6 @@ __global__ __launch_bounds__(256) void k_dedup_gather(const uint32_t* __restrict
   }
 }
 
-
 // ---------------------------------------------- pre-tokenise + dedup, one pass --
 // (round 5) HF's BpeTrainer trains on distinct words x counts, yet the pipeline above writes every
 // word occurrence (K5: 36.9 M words, 210 MB of byte symbols and 295 MB of starts / lengths, after
@@ -622,14 +587,13 @@ __global__ __launch_bounds__(64 * PD_WAVES) void k_pretok_dedup(const long long*
   __shared__ uint8_t s_lut[256];
   __shared__ uint32_t lkey[PD_LDS], lcnt[PD_LDS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lut[i] = i < lut_n ? lut[i] : (uint8_t)CLS_OTHER;
+  beast_pt::stage_lut256(s_lut, lut, lut_n);
   for (int i = threadIdx.x; i < PD_LDS; i += blockDim.x) { lkey[i] = 0; lcnt[i] = 0; }
   __syncthreads();
   PtLdsT<LC>& L = lds[wv];
   const uint64_t mask = ws.cap - 1;
   const uint32_t tag_mask = (1u << ws.tag_bits) - 1u;
   unsigned long long nwords = 0, nsyms = 0;
-  constexpr int PF = LC / 64;
   // the 512 kernel runs after the 256 one and takes only the rows that one left (257..512 code
   // points); it returns at once when there were none (the flag, a kernel boundary ago)
   if (LC > 256 && !(ws.info[3] & PD_LONG)) return;   // uniform: before any barrier
@@ -640,39 +604,13 @@ __global__ __launch_bounds__(64 * PD_WAVES) void k_pretok_dedup(const long long*
       if (lane == 0) atomicOr(&ws.info[3], PD_LONG);
       continue;
     }
-    bool bad = n64 > LC || r0 + n64 > 0xFFFFFFFFll;
+    const bool bad = n64 > LC || r0 + n64 > 0xFFFFFFFFll;
     const int n = bad ? 0 : (int)n64;
-    // 1. code points, classes, UTF-8 symbol offsets (k_pretok_wave)
-    long long tv[PF];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) tv[k] = (lane + 64 * k < n) ? tok[r0 + lane + 64 * k] : 0;
-    int carry = 0;
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-      if (64 * k >= n) break;
-      const int i = 64 * k + lane;
-      int len = 0;
-      if (i < n) {
-        const long long c = tv[k] - mn;
-        bad |= (c < 0) | (c > 0x7FFFFFFFLL);
-        L.cp[i] = (int32_t)c;
-        L.cls[i] = (c >= 0 && c < 256) ? s_lut[c] : (c >= 0 && c < lut_n) ? lut[c] : (uint8_t)CLS_OTHER;
-        len = utf8_len(c);
-      }
-      int tot;
-      const int ex = beast_pt::wave_excl_scan(len, lane, tot);
-      if (i < n) L.so[i] = (int16_t)(carry + ex);
-      carry += tot;
-    }
-    if (__any(bad)) {   // wave-uniform: the host takes the two-pass path
+    const int carry = pt_pretok_row(L, tok + r0, n, bad, lane, mn, s_lut, lut, lut_n);   // steps 1-3
+    if (carry < 0) {   // wave-uniform: the host takes the two-pass path
       if (lane == 0) atomicOr(&ws.info[3], PD_UNSUPPORTED);
       continue;
     }
-    if (lane == 0) L.so[n] = (int16_t)carry;
-    pt_wave_sync();
-    // 2. word ends, 3. the word chain (csrc/pretok.h)
-    beast_pt::regex_ends(L.cp, L.cls, L.wcp, L.e, n, lane);
-    beast_pt::word_starts(L.e, L.vis, L.wcp, nullptr, &L.nw, n, lane);
     const int nw = L.nw;
     nwords += nw;
     nsyms += carry;
@@ -729,7 +667,7 @@ __global__ __launch_bounds__(64 * PD_WAVES) void k_pretok_dedup(const long long*
         if (!done) atomicAdd(&ws.cnt[k], 1u);
       }
     }
-    pt_wave_sync();   // LDS is reused by the next sequence
+    wave_sync();   // LDS is reused by the next sequence
   }
   if (lane == 0) {
     atomicAdd(&ws.info[1], nwords);
@@ -903,13 +841,7 @@ __global__ __launch_bounds__(256) void k_copy_words_cp(const uint32_t* __restric
     const long long* src = tok + rep[w];
     uint16_t* dst = osym + offs[i];
     uint32_t o = 0;
-    auto emit = [&](long long t) {
-      uint8_t b[4];
-      const long long cp = t - mn;
-      const int Lb = utf8_len(cp);
-      utf8_bytes(cp, b);
-      for (int q = 0; q < Lb; ++q) dst[o++] = byte2id[b[q]];
-    };
+    auto emit = [&](long long t) { o += emit_utf8_ids(t - mn, byte2id, dst + o); };
     constexpr int CP_REG = 12;   // the first code points' loads all in flight (99.9 % of K5's words)
     long long c[CP_REG];
 #pragma unroll
@@ -934,7 +866,6 @@ __global__ __launch_bounds__(256) void k_word_sig(const uint16_t* __restrict__ s
 }
 
 }  // namespace
-
 
 // =================================================================== C-ABI ==
 extern "C" int beast_i64_minmax(const int64_t* x, int64_t n, int64_t* out2, void* stream) {

@@ -131,12 +131,7 @@ __device__ __forceinline__ void stage_rows(void* lds, const void* base, int64_t 
 // The single definition of what the kernels must agree on bit for bit (tokens of k_roundtrip equal
 // k_encode_v's equal k_encode's, positions likewise); the lane quantiser is beast::quantize_bins.
 
-// A wave's LDS writes become visible to its other lanes (wave-private images: no workgroup barrier).
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using beast::wave_sync;   // common.h: a wave's LDS writes become visible to its other lanes
 
 // Dequantise LUT: lut[t] = t / (vocab - 1), IEEE-divided once per workgroup (nt threads).
 __device__ __forceinline__ void lut_fill(float* lut, int lut_n, float vm1, int nt) {

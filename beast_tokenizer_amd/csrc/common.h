@@ -32,6 +32,13 @@ int comm_max_i32(beast_comm* comm, int v, int* out, hipStream_t s);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// A wave's LDS writes become visible to its other lanes (wave-private images: no workgroup barrier).
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // torch.clamp(x, min=lo_tensor, max=hi_tensor): std::min(std::max(x, lo), hi) with
 // NaN propagation (ATen clamp kernel; NaN bounds -> NaN).
 __device__ __forceinline__ float clamp_t(float x, float lo, float hi) {

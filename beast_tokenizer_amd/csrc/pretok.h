@@ -1,20 +1,65 @@
-// Shared by the BPE kernels that pre-tokenise rows (bpe_codec.hip: inference, bpe_setup.hip:
-// training): the GPT-2 / ByteLevel regex evaluated from every code point at once and the
-// lane-parallel walk of its word chain.
+// The ByteLevel row pre-tokeniser of every BPE kernel that stages a row (training: k_pretok_wave,
+// k_pretok_dedup in bpe_setup.hip; inference: k_bpe_encode, k_bpe_words through bpe_codec_device.h's
+// pretok_row), one wave per row.  Front half: class lookup, UTF-8 helpers and stage_row (code points,
+// classes, UTF-8 symbol offsets in one pass); back half: regex_ends (the GPT-2 regex from every code
+// point at once) and word_starts (the lane-parallel walk of its word chain).  The callers own
+// their LDS layouts: nothing here declares an LDS array.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "common.h"
+
 namespace beast_pt {
+
+using beast::wave_sync;
 
 constexpr int CLS_OTHER = 0, CLS_LETTER = 1, CLS_NUMBER = 2, CLS_WS = 3;
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+// The first 256 entries of the class LUT into the workgroup's LDS (every BEAST bin of a 256
+// vocab); the caller's __syncthreads follows.
+template <class N>
+__device__ __forceinline__ void stage_lut256(uint8_t* s_lut, const uint8_t* __restrict__ lut, N lut_n) {
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lut[i] = i < lut_n ? lut[i] : (uint8_t)CLS_OTHER;
+}
+
+// class of a code point from the LUT in memory alone (pretok_serial: no LDS head)
+template <class T, class N>
+__device__ __forceinline__ int class_global(T cp, const uint8_t* __restrict__ lut, N lut_n) {
+  return (cp >= 0 && cp < lut_n) ? lut[cp] : CLS_OTHER;
+}
+
+// class of a code point: the LDS head for cp < 256, the LUT in memory up to lut_n, CLS_OTHER past it
+template <class T, class N>
+__device__ __forceinline__ int class_of(T cp, const uint8_t* s_lut, const uint8_t* __restrict__ lut, N lut_n) {
+  return (cp >= 0 && cp < 256) ? s_lut[cp] : class_global(cp, lut, lut_n);
+}
+
+template <class T>
+__device__ __forceinline__ int utf8_len(T cp) { return cp < 0x80 ? 1 : cp < 0x800 ? 2 : cp < 0x10000 ? 3 : 4; }
+
+// The UTF-8 bytes of a code point, first byte lowest: one register, no indexed array (which a
+// kernel short of VGPRs would keep in scratch).
+template <class T>
+__device__ __forceinline__ uint32_t utf8_bytes(T cp) {
+  const uint32_t c = (uint32_t)cp, t0 = 0x80u | (c & 0x3F), t1 = 0x80u | ((c >> 6) & 0x3F), t2 = 0x80u | ((c >> 12) & 0x3F);
+  if (cp < 0x80) return c & 0xFFu;
+  if (cp < 0x800) return ((0xC0u | (c >> 6)) & 0xFFu) | (t0 << 8);
+  if (cp < 0x10000) return ((0xE0u | (c >> 12)) & 0xFFu) | (t1 << 8) | (t0 << 16);
+  return ((0xF0u | (c >> 18)) & 0xFFu) | (t2 << 8) | (t1 << 16) | (t0 << 24);
+}
+
+// A code point's UTF-8 bytes as vocab ids through a byte -> id table, written to dst[0 .. len);
+// returns len.  Id: uint16_t in training (global memory), int32_t in inference (LDS; -1 = the
+// byte-level char is not in the vocab, kept by an int32_t dst and narrowed to 0xFFFF by a uint16_t one).
+template <class T, class Id, class Out>
+__device__ __forceinline__ int emit_utf8_ids(T cp, const Id* __restrict__ byte2id, Out* __restrict__ dst) {
+  const int len = utf8_len(cp);
+  uint32_t b = utf8_bytes(cp);
+  for (int q = 0; q < len; ++q, b >>= 8) dst[q] = (Out)byte2id[b & 0xFFu];
+  return len;
 }
 
 // GPT-2 regex from code point i of [.., n): returns the end of the word.
@@ -59,9 +104,41 @@ __device__ __forceinline__ int wave_excl_scan(int v, int lane, int& total) {
   return x - v;
 }
 
+// One wave stages a row of n code points (row[0 .. n), all 64 lanes call).  The first 64 * PF
+// loads are issued before any is used.  code_point(i, token) is the caller's: it stores the code
+// point and its class (class_of) in the caller's image, accumulates the caller's own validity
+// flags and returns the code point's UTF-8 length.  The lengths are scanned in the same loop, from
+// the register, into so[i] = the first byte symbol of code point i, so[n] = the row's byte
+// symbols, which is also the return value.  Rows longer than 64 * PF go on chunk by chunk with
+// direct loads (inference rows only: the training kernels skip rows of more than LC = 64 * PF code
+// points before the call).  The caller's wave_sync follows.
+template <int PF, class Off, class F>
+__device__ __forceinline__ int stage_row(const long long* __restrict__ row, int n, int lane, Off* so, F&& code_point) {
+  long long tv[PF];
+#pragma unroll
+  for (int k = 0; k < PF; ++k) tv[k] = (lane + 64 * k < n) ? row[lane + 64 * k] : 0;
+  int carry = 0;
+  auto chunk = [&](int i, long long t) {
+    const int len = i < n ? code_point(i, t) : 0;
+    int tot;
+    const int ex = wave_excl_scan(len, lane, tot);
+    if (i < n) so[i] = (Off)(carry + ex);
+    carry += tot;
+  };
+#pragma unroll
+  for (int k = 0; k < PF; ++k) {
+    if (64 * k >= n) break;
+    chunk(64 * k + lane, tv[k]);
+  }
+  for (int base = 64 * PF; base < n; base += 64) chunk(base + lane, base + lane < n ? row[base + lane] : 0);
+  if (lane == 0) so[n] = (Off)carry;
+  return carry;
+}
+
 // e[i] = regex_word(cps, cls, i, n) for every i, without the per-position class-run loops: the
 // end of each class run comes from one ballot per 64 positions (run[p] = one past the last
 // position of p's run; scratch [n]), so every lane's regex end is a few independent reads.
+// Every caller passes its wcp array as run: wcp is scratch until word_starts fills it.
 __device__ __forceinline__ void regex_ends(const int32_t* cps, const uint8_t* cls, int32_t* run, int32_t* e, int n,
                                            int lane) {
   int carry = n;   // one past the first run end in the chunks after the current one
@@ -113,6 +190,9 @@ __device__ __forceinline__ void regex_ends(const int32_t* cps, const uint8_t* cl
 // on that walk, or the entry itself when the chain jumps the segment.  A marked entry below ws is
 // a mark of an older walk (e.g. "x!'tion": the walk from "'" marks "t" before the chain is known
 // to enter at "t"), so only a marked entry at or past ws reuses the walk; anything else re-walks.
+// wcp [n + 1] may have been regex_ends' run scratch (it is read no more once e is written).  wspec:
+// the words' special-token ids, all set to -1 here -- k_bpe_encode passes its array, k_bpe_words
+// and the training kernels have no special tokens and pass null.
 __device__ __forceinline__ void word_starts(const int32_t* e, uint8_t* vis, int32_t* wcp, int32_t* wspec,
                                             int32_t* nw_out, int n, int lane) {
   const int G = (n + 63) >> 6;

@@ -194,6 +194,34 @@ def test_encode_punct_contractions_live_hf(seed, encode_mode, gpu_device):
     assert not bad, f"{len(bad)} rows differ, first {texts[bad[0]]!r}"
 
 
+def test_encode_ragged_row_lengths_live_hf(encode_mode, gpu_device):
+    """The shared row staging (csrc/pretok.h stage_row) at its edges in both inference kernels: the
+    64-lane chunk (63 / 64 / 65), the four-deep prefetch boundary (255 / 256 / 257) and the
+    direct-load tail past it (300, 511 / 512 / 513), plus random short rows.  The alphabet of
+    test_bpe_pretok_ragged_rows_match_oracle (letters, digits, blank runs, the apostrophe with
+    contraction letters, punctuation, six Latin-1 two-byte code points); live HF trained on the rows."""
+    from tokenizers import ByteLevelBPETokenizer
+    from tokenizers.trainers import BpeTrainer
+    rng = np.random.default_rng(5)
+    alphabet = np.array([ord(c) for c in "ab z09 '  \t\nstrevmld!?,."] + [0xA0, 0xC4, 0xE9, 0xB5, 0xD7, 0x85])
+    lens = [1, 2, 63, 64, 65, 255, 256, 257, 300, 511, 512, 513] + list(rng.integers(1, 300, 12))
+    rows = [alphabet[rng.integers(0, alphabet.size, n)].tolist() for n in lens]
+    texts = ["".join(map(chr, r)) for r in rows]
+    tok = ByteLevelBPETokenizer()
+    tr = BpeTrainer(vocab_size=900, min_frequency=2, show_progress=False, special_tokens=[],
+                    initial_alphabet=[chr(i) for i in range(256)])
+    tok._tokenizer.train_from_iterator(texts, trainer=tr)
+    model = GpuBpeModel(tok, gpu_device)
+    got, status = encode_rows(model, rows, gpu_device)
+    assert not status.any()
+    want = [e.ids for e in tok.encode_batch(texts, add_special_tokens=False)]
+    bad = [lens[i] for i in range(len(rows)) if got[i] != want[i]]
+    assert not bad, f"rows of lengths {bad} differ"
+    dec, counts, _ = decode_rows(model, want, gpu_device, max(lens))
+    assert counts.tolist() == lens
+    assert dec == rows
+
+
 def _trained_model(span, rows, width, vocab, seed, gpu_device):
     from tokenizers import ByteLevelBPETokenizer
     from tokenizers.trainers import BpeTrainer

@@ -1,6 +1,6 @@
 """Where k_bpe_encode's time goes (tools only): variants of libbeast_hip.so built with
--DBPE_STAMPS (s_memtime at phase boundaries of row 0), -DBPE_SKIP_MERGE (no merge loop) and
--DBPE_SERIAL_PRETOK (lane-0 regex walk), timed on the bench's BPE corpus.
+-DBPE_STAMPS (s_memtime at phase boundaries of row 0) and -DBPE_SKIP_MERGE (no merge loop), timed
+on the bench's BPE corpus.
 
     python tools/codec/codec_variants.py build     # here (cross-compile)
     python tools/codec/codec_variants.py run       # on the GPU box
@@ -14,8 +14,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
-VARIANTS = {"base": [], "stamps": ["-DBPE_STAMPS"], "skip_merge": ["-DBPE_SKIP_MERGE"],
-            "serial_pretok": ["-DBPE_SERIAL_PRETOK"]}
+VARIANTS = {"base": [], "stamps": ["-DBPE_STAMPS"], "skip_merge": ["-DBPE_SKIP_MERGE"]}
 
 
 def build():
