@@ -43,7 +43,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .base_tokenizer import TokenizerBase
-from .bspline import DeviceBasis
+from .bspline import DeviceBasis, built
 
 CONFIG_FILENAME = "beast_tokenizer_config.json"
 
@@ -359,6 +359,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
                 or p.llm != self.llm_vocab_size):
             p = _Plan(self, dev)
             if p.cacheable():
+                built(dev)   # a cached plan's constants are complete before another stream can be handed them
                 self._plans[dev.index] = p
         self._plan_hot = p if p.cacheable() else None
         return p
@@ -373,6 +374,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
             order = self.joint_indices + self.gripper_indices
             src = torch.tensor(order, dtype=torch.int32, device=dev)
             hit = (src, src.clone())  # dof_src (encode) == dof_dst (reconstruct)
+            built(dev)
             self._dof_cache[dev] = hit
         return hit
 
@@ -424,6 +426,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
             c = (torch.tensor(self.joint_indices, dtype=torch.int32, device=dev),
                  self.times.to(dev, torch.float32).reshape(-1).contiguous(),
                  self._basis.knots(dev, 0).to(torch.float32).contiguous())
+            built(dev)
             self._cond_cache = {key: c}
         return c
 
@@ -478,12 +481,14 @@ class BEASTBsplineTokenizer(TokenizerBase):
             if full is None:
                 self._full_deriv = {k: v for k, v in self._full_deriv.items() if k[:2] == key[:2]}
                 full = self._full_deriv[key] = self._basis.full_deriv_basis_at(self.times.to(dev).reshape(-1), order)
+                built(dev)
         elif times is None:
             key = (dev, self._times_version)
             full = self._full_basis.get(key)
             if full is None:
                 self._full_basis = {key: self._basis.full_basis_at(self.times.to(dev).reshape(-1))}
                 full = self._full_basis[key]
+                built(dev)
         elif order:
             full = self._basis.full_deriv_basis_at(times.to(dev, dtype=torch.float32), order).contiguous()
         else:   # [T] or per-row [B, T] grids -> [T, C] / [B, T, C]

@@ -189,6 +189,9 @@ class GpuBpeModel:
         self.tok_skip = torch.from_numpy(skip).to(device)
         tid = tokenizer.token_to_id("<unk>")
         self.decode_unk_id = -1 if tid is None else int(tid)
+        # the tables above were built on the current stream (the merge map by a kernel); the model is
+        # cached and used from whatever stream is current later, so it is complete before it is returned
+        torch.cuda.current_stream(device).synchronize()
 
     @staticmethod
     def _validate(spec) -> None:

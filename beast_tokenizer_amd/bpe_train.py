@@ -94,8 +94,14 @@ class GpuBpeOps:
 
     def __init__(self, device: torch.device):
         self.device = torch.device(device)
-        self.stream = _lib.stream_of(self.device)
         self._host = torch.empty(4, dtype=torch.int64, pin_memory=True)
+
+    @property
+    def stream(self) -> int:
+        """The current stream of the device at every launch: the host reads below synchronise
+        ``torch.cuda.current_stream``, so a handle kept from construction would agree with them only
+        while nobody changed the stream in between."""
+        return _lib.stream_of(self.device)
 
     # -- small helpers
     def _read_i64(self, t: torch.Tensor, n: int) -> List[int]:

@@ -25,6 +25,13 @@ def knot_vector(degree: int, num_basis: int) -> torch.Tensor:
     return torch.cat([torch.zeros(degree), inner, torch.ones(degree)]).to(torch.float32)
 
 
+def built(device: torch.device) -> None:
+    """The last step of building a constant that is cached and later handed to whatever stream is
+    current then: wait for the stream that built it (kernels and copies are asynchronous), so the
+    cached value is complete for every stream.  Cache-miss paths only; a hit pays nothing."""
+    torch.cuda.current_stream(device).synchronize()
+
+
 class DeviceBasis:
     """Basis / projection cache for one tokenizer (joint degree p, gripper degree 0).
 
@@ -154,6 +161,7 @@ class DeviceBasis:
             hit = torch.zeros((3, 2, t.numel(), self.num_basis), dtype=torch.float32, device=times.device)
             for o in range(3):
                 hit[o, : self.n_kinds] = self.deriv_basis_at(t, o)
+            built(times.device)
             self._cache[key] = hit
         return hit
 
@@ -249,6 +257,7 @@ class DeviceBasis:
                 raise IndexError("index 1 is out of bounds for dimension 1 with size 1")
             self.conditioned_projection(times.reshape(-1).to(torch.float32), phi[0], proj)
         hit = (phi, proj, proj.to(torch.float32))
+        built(times.device)
         self._cache[key] = hit
         return hit
 

@@ -26,8 +26,12 @@ class GpuQuantileOps:
 
     def __init__(self, device: torch.device):
         self.device = device
-        self.stream = _lib.stream_of(device)
         self.lib = _lib.load()
+
+    @property
+    def stream(self) -> int:
+        """The current stream of the device at every launch (not the one of construction)."""
+        return _lib.stream_of(self.device)
 
     def prepare(self, x, n_total: int, qs: Sequence[float]) -> None:
         """x: one [rows, cols] fp32 tensor, or a list of them (row segments, read in place)."""

@@ -266,13 +266,18 @@ def test_host_fastpath_equals_python_path(name, gpu_device):
         p.fast, p.fast_enc, p.fast_rec = saved
     assert torch.equal(t1, t2) and torch.equal(d1["params"], d2["params"]) and torch.equal(r1, r2)
     assert list(d1) == list(d2) and all(d1[k] is None for k in d1 if k != "params")   # same dict as the reference
-    # the fastcall entry points run on a non-default current stream too
-    s = torch.cuda.Stream(device=gpu_device)
-    with torch.cuda.stream(s):
-        t6, _ = tok.encode(xd)
-        r6 = tok.reconstruct_traj(t6)
-    s.synchronize()
-    assert torch.equal(t6, t1) and torch.equal(r6, r1)
+    # the fastcall entry points are ordered on a non-default current stream: the ordering probe of
+    # tests/stream_order.py (stale input, a delay, poison-free fresh outputs, no host synchronisation)
+    from stream_order import Case, assert_ordered
+    xb = torch.empty_like(xd)
+
+    def chain(_handle):
+        t6, d6 = tok.encode(xb)
+        return [t6, d6["params"], tok.reconstruct_traj(t6)]
+    rep = assert_ordered(Case(f"fastpath[{name}]", ("fast_encode", "fast_reconstruct"),
+                              [(xb, xd, xd.flip(0).contiguous())], chain), gpu_device, api=True)
+    assert torch.equal(rep.snapshot[0], t1) and torch.equal(rep.snapshot[1], d1["params"])
+    assert torch.equal(rep.snapshot[2], r1)
     # fall-through cases: host input, strided input, 3-D int32 tokens
     t3, _ = tok.encode(x)
     assert torch.equal(t3, t1)
