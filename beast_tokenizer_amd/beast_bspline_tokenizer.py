@@ -222,6 +222,53 @@ class _ReconstructContinuous(torch.autograd.Function):
         return (grad_params if ctx.needs_input_grad[0] else None, grad_ip) + none[2:]
 
 
+def _logits_expect(logits, temperature, tok_offset, want_mean, want_tokens, want_stats):
+    """One launch of ``beast_logits_expect`` on the current stream of the logits' device.
+    ``logits`` is [B, K, V] fp32 / fp16 / bf16 on a ROCm device with unit last stride (any view: its
+    strides go to the kernel).  Returns (mean, tokens, stats), None where not requested."""
+    B, K, V = logits.shape
+    dev = logits.device
+    mean = torch.empty((B, K), dtype=torch.float32, device=dev) if want_mean else None
+    tokens = torch.empty((B, K), dtype=torch.int64, device=dev) if want_tokens else None
+    stats = torch.empty((B, K, 2), dtype=torch.float32, device=dev) if want_stats else None
+    if B > 0:
+        _lib.run("beast_logits_expect", logits.data_ptr(), _lib.LOGITS_DTYPES[logits.dtype], B, K, V,
+                 logits.stride(0), logits.stride(1), temperature, tok_offset, _lib.ptr(mean), _lib.ptr(tokens),
+                 _lib.ptr(stats), _lib.stream_of(dev))
+    return mean, tokens, stats
+
+
+class _ExpectedParams(torch.autograd.Function):
+    """``expected_params_from_logits`` with a backward: one launch of ``beast_logits_expect`` (mean and
+    the row statistics, the greedy tokens too when asked for) forward, one of ``beast_logits_expect_bwd``
+    backward.  ``logits`` is what ``_logits_expect`` takes; the move, reshape, slice and cast that made
+    it lie outside, so autograd carries the gradient back to the leaf's own shape, dtype and place."""
+
+    @staticmethod
+    def forward(ctx, logits, temperature, want_tokens):
+        mean, tokens, stats = _logits_expect(logits, temperature, 0, True, want_tokens, True)
+        ctx.save_for_backward(logits, mean, stats)
+        ctx.temperature = temperature
+        if tokens is None:
+            return mean
+        ctx.mark_non_differentiable(tokens)
+        return mean, tokens
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_mean, *_):
+        logits, mean, stats = ctx.saved_tensors
+        B, K, V = logits.shape
+        dev = logits.device
+        grad = torch.empty((B, K, V), dtype=logits.dtype, device=dev)
+        if B > 0:
+            g = grad_mean.to(device=dev, dtype=torch.float32).contiguous()   # a stride-0 expansion becomes rows
+            _lib.run("beast_logits_expect_bwd", logits.data_ptr(), _lib.LOGITS_DTYPES[logits.dtype], B, K, V,
+                     logits.stride(0), logits.stride(1), ctx.temperature, mean.data_ptr(), stats.data_ptr(),
+                     g.data_ptr(), grad.data_ptr(), K * V, V, _lib.stream_of(dev))
+        return grad, None, None
+
+
 class BEASTBsplineTokenizer(TokenizerBase):
 
     def __init__(self, num_dof=1, num_basis=10, duration=2 * torch.pi, seq_len=50, vocab_size=256,
@@ -1162,6 +1209,89 @@ class BEASTBsplineTokenizer(TokenizerBase):
                 ip = self._init_p_rows(init_p, params.shape[0], p)
                 return _ReconstructContinuous.apply(params, ip, self, p, times, orders)
             return self._reconstruct_derivs(None, params, times, orders, init_p, False, p)
+
+    # ===============================================
+    #          - decoding from logits -
+    # ===============================================
+
+    def _check_logits(self, logits) -> None:
+        """Shape and dtype of a logits argument; raised before the device is asked for."""
+        K = self.num_basis * self.num_dof
+        if not isinstance(logits, torch.Tensor) or not logits.dtype.is_floating_point:
+            raise ValueError("logits must be a floating-point tensor")
+        if logits.dtype not in _lib.LOGITS_DTYPES and logits.dtype is not torch.float64:
+            raise ValueError(f"logits must be float32, float16, bfloat16 or float64; got {logits.dtype}")
+        shape = tuple(logits.shape)
+        if shape[1:-1] not in ((K,), (self.num_basis, self.num_dof)) or len(shape) < 3:
+            raise ValueError(f"logits must be [B, {K}, V] or [B, {self.num_basis}, {self.num_dof}, V]; got {shape}")
+        widths = {self.vocab_size} | ({self.llm_vocab_size} if self.llm_vocab_size is not None else set())
+        if shape[-1] not in widths:
+            raise ValueError(f"the last dimension of logits must be vocab_size {self.vocab_size}"
+                             + (f" or llm_vocab_size {self.llm_vocab_size}" if self.llm_vocab_size is not None else "")
+                             + f"; got {shape[-1]}")
+
+    def _logits_rows(self, logits, dev: torch.device) -> torch.Tensor:
+        """The action logits as the kernel reads them: [B, N*D, vocab_size] on ``dev``, fp32 / fp16 /
+        bf16, unit last stride.  A full-vocabulary tensor gives the VIEW of its action slice
+        [llm_vocab_size - vocab_size, llm_vocab_size): its strides go to the kernel, nothing is copied.
+        Every step is a torch op, so under autograd the gradient finds its way back to the leaf."""
+        if logits.device != dev:
+            logits = logits.to(dev)
+        if logits.dim() == 4:
+            logits = logits.reshape(logits.shape[0], -1, logits.shape[-1])
+        if logits.shape[-1] != self.vocab_size:
+            logits = logits[..., self.llm_vocab_size - self.vocab_size:]
+        if logits.dtype is torch.float64:
+            logits = logits.to(torch.float32)
+        return logits if logits.stride(2) == 1 else logits.contiguous()
+
+    @staticmethod
+    def _check_temperature(temperature) -> float:
+        t = float(temperature)
+        if not (t > 0.0 and t < float("inf")):
+            raise ValueError(f"temperature must be finite and > 0; got {temperature!r}")
+        return t
+
+    def expected_params_from_logits(self, logits, *, temperature=1.0, return_tokens=False):
+        """The expected normalised coefficients under ``softmax(logits / temperature)``: fp32
+        [B, N*D] in (n d) order, the input of ``reconstruct_traj_continuous`` /
+        ``reconstruct_traj_continuous_derivs``; with ``return_tokens`` also the greedy MP tokens
+        (int64 [B, N*D], lowest bin on ties), from the same launch.
+
+        ``logits`` is [B, N*D, V'] or [B, N, D, V'] with V' == vocab_size, or V' == llm_vocab_size
+        when one is set (the action slice is then read in place).  fp32, fp16 and bf16 go to the
+        kernel as they are.  Differentiable in ``logits`` (one launch of ``beast_logits_expect_bwd``,
+        DESIGN.md §4); without ``requires_grad`` or under ``no_grad`` no graph is recorded."""
+        self._check_logits(logits)
+        temperature = self._check_temperature(temperature)
+        p = self._plan()
+        grad = torch.is_grad_enabled() and logits.requires_grad
+        with torch.set_grad_enabled(grad):
+            rows = self._logits_rows(logits, p.dev)
+            if grad:
+                return _ExpectedParams.apply(rows, temperature, bool(return_tokens))
+            mean, tokens, _ = _logits_expect(rows, temperature, 0, True, bool(return_tokens), False)
+            return (mean, tokens) if return_tokens else mean
+
+    def reconstruct_traj_from_logits(self, logits, times=None, *, temperature=1.0, orders=None, init_p=None):
+        """The trajectory of the expected coefficients: ``reconstruct_traj_continuous`` (``orders``
+        None: positions [B, T, num_dof]) or ``reconstruct_traj_continuous_derivs`` (one tensor per
+        requested order) applied to ``expected_params_from_logits``.  A trajectory-space loss reaches
+        the logits through the two fused backward launches."""
+        ntokens = self.expected_params_from_logits(logits, temperature=temperature)
+        if orders is None:
+            return self.reconstruct_traj_continuous(ntokens, times=times, init_p=init_p)
+        return self.reconstruct_traj_continuous_derivs(ntokens, times=times, orders=orders, init_p=init_p)
+
+    @torch.no_grad()
+    def greedy_tokens_from_logits(self, logits, *, respect_llm_vocab_size=True):
+        """Greedy tokens int64 [B, N*D]: the lowest bin that holds a row's maximum, over the action
+        range only, plus the LLM offset exactly as ``encode`` adds it.  The same kernel with only its
+        argmax output; never differentiable."""
+        self._check_logits(logits)
+        p = self._plan()
+        rows = self._logits_rows(logits, p.dev)
+        return _logits_expect(rows, 1.0, self._offset(respect_llm_vocab_size), False, True, False)[1]
 
     # ===============================================
     #           - tokenizer evaluation -

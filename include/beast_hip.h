@@ -272,6 +272,61 @@ int beast_reconstruct_derivs_bwd_f32(const float* grad_pos, const float* grad_ve
                                      float* grad_ntokens, float* grad_init_p, int64_t grad_init_p_sb,
                                      void* stream);
 
+/* Decode from logits: the bridge from a discrete head's logits to the normalised coefficients
+ * that beast_reconstruct_f32 / beast_reconstruct_derivs_f32 take as `ntokens` (and
+ * beast_reconstruct_derivs_bwd_f32 differentiates).  The reference has no counterpart.  For one
+ * token row l[0..V) (token k = n*D + d of trajectory b) and tau = temperature > 0:
+ *   z_v  = l_v / tau      zmax = max_v z_v      e_v = exp(z_v - zmax)      s = sum_v e_v
+ *   mean = clamp(sum_v e_v * x_v / s, -1, 1),   x_v = 2v/(V-1) - 1
+ *   amax = the lowest v with l_v == max_v l_v   (on the raw logits: no rounding enters)
+ *   grad_l_v = (g / tau) * (e_v / s) * (x_v - mean)      (g: the upstream gradient of mean)
+ * In exact arithmetic mean lies in [-1, 1]; the clamp only removes an fp32 overshoot (which the
+ * mask of beast_reconstruct_derivs_bwd_f32 would turn into a zero gradient) and its derivative is
+ * taken as 1.  A -inf entry has probability exactly 0 and gradient exactly 0.  A row that holds a
+ * NaN or +inf, or only -inf, yields unspecified values in ITS OWN outputs; it does not fault and
+ * does not disturb any other row.  Arithmetic is fp32 whatever the element type.  Where one bin
+ * holds the mass, x_v - mean cancels; the backward therefore measures x_v and the mean from the
+ * bin nearest to the forward's mean (exact integers, one more sum over the row), so a peaked row's
+ * gradient keeps its relative accuracy instead of inheriting the rounding of the fp32 mean.
+ *   logits      [B][K][V] of `dtype` (BEAST_LOGITS_*), element strides sb, sk >= 0; the V axis has
+ *               stride 1.  Each row is read from memory ONCE per direction, for every V, with
+ *               16-byte loads where the row's own address is 16-byte aligned and element loads
+ *               where it is not (alignment is a per-row property: a bf16 slice with a 600-byte row
+ *               stride alternates).
+ *   tok_offset  added to amax (the LLM-vocabulary offset, as in beast_encode_f32)
+ *   mean_out    nullable [B][K]     normalised, in [-1, 1]
+ *   argmax_out  nullable [B][K]     amax + tok_offset
+ *   stats_out   nullable [B][K][2]  (zmax, s): the backward's input
+ *   At least one of the three outputs is non-null.
+ *   grad_mean   [B][K] contiguous;  mean, stats: what the forward wrote for the same logits
+ *   grad_logits [B][K][V] of `dtype`, element strides gsb >= 0, gsk >= V (rows must not overlap),
+ *               V stride 1; every element of every row is written and nothing around it.
+ * One wave owns a row; element v always belongs to lane (v / (16 / sizeof(T))) % 64 and every sum
+ * has an order fixed by (V, dtype) alone -- no atomics, no LDS -- so a row's outputs are bitwise
+ * identical alone or in any batch, at any alignment, in any grid and from run to run.
+ * hip_stream is the `stream` of the conventions above.  Envelope: 2 <= V <= 65536, else
+ * BEAST_E_UNSUPPORTED; temperature must be finite and > 0; B = 0 returns 0 without a launch. */
+#define BEAST_LOGITS_F32 0
+#define BEAST_LOGITS_F16 1
+#define BEAST_LOGITS_BF16 2
+
+int beast_logits_expect(const void* logits, int dtype, int64_t B, int K, int V,
+                        int64_t sb, int64_t sk,
+                        float temperature, int64_t tok_offset,
+                        float* mean_out, int64_t* argmax_out, float* stats_out,
+                        void* hip_stream);
+
+int beast_logits_expect_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                            float temperature, const float* mean, const float* stats,
+                            const float* grad_mean,
+                            void* grad_logits, int64_t gsb, int64_t gsk,
+                            void* hip_stream);
+
+/* Rows that one launch of beast_logits_expect (backward != 0: of beast_logits_expect_bwd) keeps
+ * resident on the stream's device for this dtype and V: a launch over more rows walks them with a
+ * grid stride.  Launches nothing.  Returns the count (> 0) or a negative BEAST_E_* code. */
+int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* hip_stream);
+
 /* Error statistics of encode -> reconstruct in ONE launch: how well the tokenizer represents the
  * trajectories, and whether the spline fit or the quantiser is to blame.  traj .. dof_src, proj,
  * N, w_min, w_max, vocab and tok_offset mean what they mean in beast_encode_f32; basis is
