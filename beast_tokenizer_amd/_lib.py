@@ -21,7 +21,7 @@ BEAST_E_INVALID = -1
 BEAST_E_HIP = -2
 BEAST_E_UNSUPPORTED = -3
 BEAST_E_WORKSPACE = -4
-ABI_VERSION = 1
+ABI_VERSION = 2
 OPT_GENERIC_KERNELS = 1
 OPT_BLOCK_WAVES = 2
 OPT_MERGE_LDS_MIN = 3
@@ -38,7 +38,7 @@ BPE_STATE_VCUR = 1
 BPE_STATE_NMERGES = 2
 BPE_STATE_PASSES = 9
 BPE_LOOP_P = 0x9E3779B97F4A7C15   # odd multiplier of the token-string hash (csrc/bpe_vocab.h LOOP_P)
-# BEAST_LOGITS_*: the element types beast_logits_expect / _bwd read as they are
+# BEAST_LOGITS_*: the element types beast_logits_expect / _bwd and beast_xent_rows / _bwd read as they are
 LOGITS_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 # kernel families of OPT_LAST_CODEC_LAUNCH (bits 0-3), in the header's order
@@ -76,6 +76,10 @@ SIGNATURES = {
     "beast_logits_expect_bwd": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _i64,
                                        _vp]),
     "beast_logits_resident_rows": (_i64, [_i32, _i32, _i32, _vp]),
+    "beast_xent_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp,
+                               _vp]),
+    "beast_xent_rows_bwd": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _i64, _f32, _vp, _vp,
+                                   _vp, _i64, _i64, _vp]),
     "beast_roundtrip_stats_f32": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
                                          _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "beast_colminmax_workspace_bytes": (_sz, [_i64, _i32]),

@@ -34,6 +34,7 @@ from __future__ import annotations
 
 import json
 import numbers
+import struct
 from pathlib import Path
 from typing import NamedTuple, Optional
 
@@ -267,6 +268,58 @@ class _ExpectedParams(torch.autograd.Function):
                      logits.stride(0), logits.stride(1), ctx.temperature, mean.data_ptr(), stats.data_ptr(),
                      g.data_ptr(), grad.data_ptr(), K * V, V, _lib.stream_of(dev))
         return grad, None, None
+
+
+def _xent_targets(target):
+    """(target_tok, target_pos) pointers of a [B, K] contiguous int64 or fp32 target."""
+    return (target.data_ptr(), None) if target.dtype is torch.int64 else (None, target.data_ptr())
+
+
+def _xent_rows(logits, target, tok_offset, ignore_index, smoothing, want_loss, want_tokens, want_stats):
+    """One launch of ``beast_xent_rows`` on the current stream of the logits' device.  ``logits`` is
+    what ``_logits_expect`` takes, ``target`` [B, K] contiguous int64 tokens or fp32 normalised
+    coefficients on the same device.  Returns (loss, tokens, stats), None where not requested."""
+    B, K, V = logits.shape
+    dev = logits.device
+    loss = torch.empty((B, K), dtype=torch.float32, device=dev) if want_loss else None
+    tokens = torch.empty((B, K), dtype=torch.int64, device=dev) if want_tokens else None
+    stats = torch.empty((B, K, 2), dtype=torch.float32, device=dev) if want_stats else None
+    if B > 0:
+        _lib.run("beast_xent_rows", logits.data_ptr(), _lib.LOGITS_DTYPES[logits.dtype], B, K, V,
+                 logits.stride(0), logits.stride(1), *_xent_targets(target), tok_offset, ignore_index, smoothing,
+                 _lib.ptr(loss), _lib.ptr(stats), _lib.ptr(tokens), _lib.stream_of(dev))
+    return loss, tokens, stats
+
+
+class _CrossEntropy(torch.autograd.Function):
+    """``cross_entropy_from_logits`` per row with a backward: one launch of ``beast_xent_rows`` (loss
+    and the row statistics, the greedy tokens too when asked for) forward, one of
+    ``beast_xent_rows_bwd`` backward.  As with ``_ExpectedParams`` the move, reshape, slice and cast
+    that made ``logits`` lie outside; the target is never differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, target, tok_offset, ignore_index, smoothing, want_tokens):
+        loss, tokens, stats = _xent_rows(logits, target, tok_offset, ignore_index, smoothing, True, want_tokens, True)
+        ctx.save_for_backward(logits, target, stats)
+        ctx.consts = (tok_offset, ignore_index, smoothing)
+        if tokens is None:
+            return loss
+        ctx.mark_non_differentiable(tokens)
+        return loss, tokens
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, *_):
+        logits, target, stats = ctx.saved_tensors
+        B, K, V = logits.shape
+        dev = logits.device
+        grad = torch.empty((B, K, V), dtype=logits.dtype, device=dev)
+        if B > 0:
+            g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()   # a stride-0 expansion becomes rows
+            _lib.run("beast_xent_rows_bwd", logits.data_ptr(), _lib.LOGITS_DTYPES[logits.dtype], B, K, V,
+                     logits.stride(0), logits.stride(1), *_xent_targets(target), *ctx.consts, stats.data_ptr(),
+                     g.data_ptr(), grad.data_ptr(), K * V, V, _lib.stream_of(dev))
+        return grad, None, None, None, None, None
 
 
 class BEASTBsplineTokenizer(TokenizerBase):
@@ -1292,6 +1345,74 @@ class BEASTBsplineTokenizer(TokenizerBase):
         p = self._plan()
         rows = self._logits_rows(logits, p.dev)
         return _logits_expect(rows, 1.0, self._offset(respect_llm_vocab_size), False, True, False)[1]
+
+    # ===============================================
+    #          - training from logits -
+    # ===============================================
+
+    def _check_xent_target(self, target, batch: int) -> None:
+        """Shape and dtype of a cross-entropy target; raised before the device is asked for."""
+        K = self.num_basis * self.num_dof
+        if not isinstance(target, torch.Tensor) or target.dtype is torch.bool or target.is_complex():
+            raise ValueError("target must be an integer tensor of tokens or a floating-point tensor of "
+                             "normalised coefficients")
+        if tuple(target.shape) not in ((batch, K), (batch, self.num_basis, self.num_dof)):
+            raise ValueError(f"target must be [{batch}, {K}] or [{batch}, {self.num_basis}, {self.num_dof}]; "
+                             f"got {tuple(target.shape)}")
+
+    def cross_entropy_from_logits(self, logits, target, *, label_smoothing=0.0, ignore_index=-100,
+                                  reduction="mean", return_tokens=False, respect_llm_vocab_size=True):
+        """The token loss of a discrete head, from one fused launch over the logits.
+
+        ``logits`` is what ``expected_params_from_logits`` takes.  The softmax runs over the
+        ``vocab_size`` action bins only: of a full-vocabulary tensor only the action slice is read,
+        and only it receives a gradient.  ``target`` is [B, N*D] or [B, N, D] and selects the loss:
+
+        * integer tokens, as ``encode`` returns them (the LLM offset is removed in the kernel
+          according to ``respect_llm_vocab_size``): the usual cross-entropy.  Rows whose token equals
+          ``ignore_index`` are ignored; any other token outside the action range gives NaN.
+        * floating-point normalised coefficients in [-1, 1] in the same (n d) order, as
+          ``encode_continuous`` returns them and ``reconstruct_traj_continuous`` takes them: the
+          two-hot target on the two bins around the coefficient, whose expectation is the coefficient
+          itself, so the optimum agrees with ``expected_params_from_logits``.  NaN coefficients are
+          ignored.
+
+        ``label_smoothing`` in [0, 1) mixes the target with the uniform distribution.  ``reduction``
+        "none" gives fp32 [B, N*D]; "sum" and "mean" reduce it with torch ops, "mean" over the rows
+        that are not ignored (NaN when there are none).  With ``return_tokens`` the greedy MP tokens
+        of the same launch come second.  Differentiable in ``logits`` (one launch of
+        ``beast_xent_rows_bwd``); without ``requires_grad`` or under ``no_grad`` no graph is recorded."""
+        self._check_logits(logits)
+        self._check_xent_target(target, logits.shape[0])
+        try:
+            smoothing = struct.unpack("f", struct.pack("f", float(label_smoothing)))[0]   # as the kernel gets it
+        except (OverflowError, TypeError, ValueError):
+            smoothing = float("nan")
+        if not 0.0 <= smoothing < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1); got {label_smoothing!r}")
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError(f"reduction must be 'none', 'sum' or 'mean'; got {reduction!r}")
+        ignore_index = int(ignore_index)
+        p = self._plan()
+        grad = torch.is_grad_enabled() and logits.requires_grad
+        off = self._offset(respect_llm_vocab_size)
+        with torch.no_grad():
+            tgt = target.detach().to(p.dev).reshape(target.shape[0], self.num_basis * self.num_dof)
+            tgt = tgt.to(torch.float32 if tgt.dtype.is_floating_point else torch.int64).contiguous()
+        with torch.set_grad_enabled(grad):
+            rows = self._logits_rows(logits, p.dev)
+            if grad:
+                out = _CrossEntropy.apply(rows, tgt, off, ignore_index, smoothing, bool(return_tokens))
+                loss, tokens = out if return_tokens else (out, None)
+            else:
+                loss, tokens, _ = _xent_rows(rows, tgt, off, ignore_index, smoothing, True, bool(return_tokens), False)
+            if reduction != "none":
+                total = loss.sum()
+                if reduction == "mean":
+                    kept = ~torch.isnan(tgt) if tgt.dtype.is_floating_point else tgt != ignore_index
+                    total = total / kept.sum()
+                loss = total
+        return (loss, tokens) if return_tokens else loss
 
     # ===============================================
     #           - tokenizer evaluation -

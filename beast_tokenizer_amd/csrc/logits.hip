@@ -26,6 +26,10 @@
 // e_v is computed as exp2((l_v * (1/tau) - zmax) * log2 e) with the product and the difference in
 // one fma, in the forward and in the backward alike: zmax (stats[0]) is the only thing the
 // backward needs to reproduce the forward's e_v.
+//
+// The same machinery carries the training direction (beast_xent_rows, beast_xent_rows_bwd): the
+// cross-entropy of a row against a token or against the two-hot target of an unquantised
+// coefficient, k_xent / k_xent_online and k_xent_bwd / k_xent_bwd_long further down.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +50,7 @@ constexpr int LG_ONLINE_U = 4;       // online form: chunks loaded before any of
 constexpr int LG_MIN_V = 2;
 constexpr int LG_MAX_V = 65536;
 constexpr float LG_LOG2E = 1.44269504088896340736f;
+constexpr float LG_LN2 = 0.693147180559945309417f;
 
 // ------------------------------------------------------------------ element types --
 struct ElemF32 {
@@ -519,6 +524,484 @@ __global__ __launch_bounds__(LG_THREADS) void k_logits_expect_bwd_long(LogitsArg
   }
 }
 
+// ------------------------------------------------------- two-hot cross-entropy kernels --
+// beast_xent_rows / beast_xent_rows_bwd on the same row machinery.  With m = max_v l_v,
+// e_v = exp(l_v - m), s = sum_v e_v and a target position u = i + f (i <= V-2, f in [0, 1]):
+//   q_v    = (1-eps) [(1-f) (v == i) + f (v == i+1)] + eps / V
+//   loss   = log s + (1-eps) [(1-f) (m - l_i) + f (m - l_{i+1})] + eps (sum_v (m - l_v)) / V
+//   grad_v = g (e_v / s - q_v)
+// Every term of the loss is >= 0: nothing cancels.  A term whose weight is exactly 0 is left out
+// by a select, so a -inf logit under a zero weight gives neither NaN nor inf.  The target only
+// ever meets v in a comparison: l_i and l_{i+1} are picked by select and the wave sum of one
+// non-zero term is exact.  The temperature is 1, so e_v is exp_shifted(l_v, 1, m) in both
+// directions and stats = (m, s) is all the backward needs.
+struct XentArgs {
+  const void* logits;
+  int64_t sb, sk;        // element strides of the batch and the token axis
+  int64_t rows;          // B * K
+  int64_t K, gK;         // folded_k of the logits' and of grad_logits' strides
+  int V;
+  float vm1;             // V - 1
+  const int64_t* tok;    // exactly one of tok, pos
+  const float* pos;
+  int64_t tok_offset, ignore_index;
+  float eps, keep, eps_v;   // label smoothing, 1 - eps, eps / V
+  float* loss;           // forward outputs, nullable
+  float* stats;          // forward: out (nullable); backward: in
+  int64_t* amax;
+  // backward only
+  const float* grad_loss;
+  void* grad;
+  int64_t gsb, gsk;
+};
+
+constexpr int XENT_TARGET = 0, XENT_IGNORED = 1, XENT_OUT_OF_RANGE = 2;
+struct XentTarget {
+  int i;       // the lower bin, <= V-2; matches no v where the row has no target
+  float f;     // the weight of bin i+1
+  int kind;
+};
+// Which two bins carry a row's target.  A coefficient x gives u = clamp(((x + 1) * 0.5) * (V-1),
+// 0, V-1) with these three roundings in fp32 (the oracle replicates them); a token t gives u = t.
+// A row's target as memory holds it: loaded at the top of a group of rows, beside the rows
+// themselves, so that its latency is not paid row by row.
+struct XentRaw {
+  int64_t tok;
+  float pos;
+};
+__device__ __forceinline__ XentRaw xent_load(const XentArgs& a, int64_t row) {
+  XentRaw r{0, 0.0f};
+  if (a.tok != nullptr) r.tok = a.tok[row];
+  else r.pos = a.pos[row];
+  return r;
+}
+__device__ __forceinline__ XentTarget xent_target(const XentArgs& a, const XentRaw& in) {
+  XentTarget t{-2, 0.0f, XENT_TARGET};
+  if (a.tok != nullptr) {
+    const int64_t raw = in.tok;
+    const int64_t tk = raw - a.tok_offset;
+    if (raw == a.ignore_index) {
+      t.kind = XENT_IGNORED;
+    } else if (tk < 0 || tk >= a.V) {
+      t.kind = XENT_OUT_OF_RANGE;
+    } else {
+      t.i = min((int)tk, a.V - 2);
+      t.f = (float)((int)tk - t.i);
+    }
+    return t;
+  }
+  const float x = in.pos;
+  if (x != x) {
+    t.kind = XENT_IGNORED;
+    return t;
+  }
+  const float u = fminf(fmaxf(__fmul_rn(__fmul_rn(__fadd_rn(x, 1.0f), 0.5f), a.vm1), 0.0f), a.vm1);
+  t.i = min((int)u, a.V - 2);             // u >= 0: the conversion is the floor
+  t.f = __fsub_rn(u, (float)t.i);         // exact
+  return t;
+}
+
+// The wave's maximum alone, and the wave's lowest index, the same value in every lane: one DPP
+// operation a step where the (value, index) pair of wave_max takes five.
+__device__ __forceinline__ float wave_max_value(float x) {
+  x = fmaxf(x, dpp_f<DPP_XOR1>(x));
+  x = fmaxf(x, dpp_f<DPP_XOR2>(x));
+  x = fmaxf(x, dpp_f<DPP_HALF_MIRROR>(x));
+  x = fmaxf(x, dpp_f<DPP_MIRROR>(x));
+  return fmaxf(fmaxf(lane_f(x, 0), lane_f(x, 16)), fmaxf(lane_f(x, 32), lane_f(x, 48)));
+}
+__device__ __forceinline__ int wave_min_index(int i) {
+  i = min(i, dpp_i<DPP_XOR1>(i));
+  i = min(i, dpp_i<DPP_XOR2>(i));
+  i = min(i, dpp_i<DPP_HALF_MIRROR>(i));
+  i = min(i, dpp_i<DPP_MIRROR>(i));
+  return min(min(__builtin_amdgcn_readlane(i, 0), __builtin_amdgcn_readlane(i, 16)),
+             min(__builtin_amdgcn_readlane(i, 32), __builtin_amdgcn_readlane(i, 48)));
+}
+
+// Element `rel` of a chunk (lane rel / EPL, slot rel % EPL) for a wave-uniform rel in [0, 64 EPL):
+// the lane by a readlane of every slot, the slot by scalar compares among the results (in this order:
+// a select chain over the register array itself would be folded into a dynamic index, which the
+// compiler serves from scratch).  The target is compared, never an address.
+template <int E>
+__device__ __forceinline__ float pick_piece(const float (&v)[E], int rel) {
+  const int ln = rel / E, j = rel & (E - 1);
+  float x = lane_f(v[0], ln);
+#pragma unroll
+  for (int k = 1; k < E; ++k) {
+    const float y = lane_f(v[k], ln);
+    x = (j == k) ? y : x;
+  }
+  return x;
+}
+
+// What lane 0 stores for a row.  li, li1: l_i and l_{i+1}; sd: sum_v (m - l_v) (eps > 0 only).
+__device__ __forceinline__ void xent_store(const XentArgs& a, int64_t row, int lane, const XentTarget& t, float m,
+                                           float s, float li, float li1, float sd, int mi) {
+  if (lane != 0) return;
+  if (a.loss != nullptr) {
+    float L = 0.0f;
+    if (t.kind == XENT_OUT_OF_RANGE) {
+      L = __builtin_nanf("");
+    } else if (t.kind == XENT_TARGET) {
+      const float w0 = __fsub_rn(1.0f, t.f);
+      float hot = 0.0f;
+      if (w0 != 0.0f) hot = __fmul_rn(w0, __fsub_rn(m, li));
+      if (t.f != 0.0f) hot = __fadd_rn(hot, __fmul_rn(t.f, __fsub_rn(m, li1)));
+      L = __fadd_rn(__fmul_rn(__builtin_amdgcn_logf(s), LG_LN2), __fmul_rn(a.keep, hot));   // s >= 1
+      if (a.eps > 0.0f) L = __fadd_rn(L, __fmul_rn(a.eps_v, sd));
+    }
+    a.loss[row] = L;
+  }
+  if (a.amax != nullptr) a.amax[row] = (int64_t)mi + a.tok_offset;
+  if (a.stats != nullptr) {
+    a.stats[2 * row] = m;
+    a.stats[2 * row + 1] = s;
+  }
+}
+
+// Rows of up to NCH chunks, R of them per wave at a time, held in registers.
+template <class T, int NCH, int R>
+__global__ __launch_bounds__(LG_THREADS) void k_xent(XentArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const bool sums = a.loss != nullptr || a.stats != nullptr;
+  const bool picks = a.loss != nullptr;
+  const bool smooth = picks && a.eps > 0.0f;
+  const int64_t ngroups = (a.rows + R - 1) / R;
+
+  for (int64_t g = (int64_t)blockIdx.x * LG_WAVES + wave; g < ngroups; g += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t off[R];
+    group_offsets<R>(g * R, a.rows, a.K, a.sb, a.sk, off);
+    XentRaw in[R];
+    if (picks) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) in[r] = xent_load(a, min(g * R + r, a.rows - 1));
+    }
+    Vec16 q[R][NCH];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const raw* rowp = static_cast<const raw*>(a.logits) + off[r];
+      const bool aligned = (reinterpret_cast<uintptr_t>(rowp) & 15) == 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) q[r][c] = load_piece<T>(rowp, aligned, c * CH + lane * E, V);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = min(g * R + r, a.rows - 1);
+      float v[NCH][E];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) unpack_piece<T>(q[r][c], c * CH + lane * E, V, v[c]);
+      // the exact maximum first; its lowest index only where the argmax is asked for
+      float mx = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < E; ++j) mx = fmaxf(mx, v[c][j]);
+      mx = wave_max_value(mx);
+      int mi = 0;
+      if (a.amax != nullptr) {
+        int first = LG_MAX_V;
+#pragma unroll
+        for (int c = NCH - 1; c >= 0; --c)
+#pragma unroll
+          for (int j = E - 1; j >= 0; --j) first = (v[c][j] == mx) ? c * CH + lane * E + j : first;
+        mi = wave_min_index(first);
+      }
+      XentTarget t{-2, 0.0f, XENT_TARGET};
+      float s = 0.0f, li = 0.0f, li1 = 0.0f, sd = 0.0f;
+      if (sums) {
+        float ls = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+          for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, exp_shifted(v[c][j], 1.0f, mx));
+        s = wave_sum(ls);
+      }
+      if (picks) {
+        t = xent_target(a, in[r]);
+        const int ti = __builtin_amdgcn_readfirstlane(t.i);            // the row's, so the wave's
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int r0 = ti - c * CH, r1 = r0 + 1;
+          if (r0 >= 0 && r0 < CH) li = pick_piece<E>(v[c], r0);
+          if (r1 >= 0 && r1 < CH) li1 = pick_piece<E>(v[c], r1);
+        }
+        if (smooth) {
+          float ld = 0.0f;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int j = 0; j < E; ++j)                                  // padding is masked
+              ld = __fadd_rn(ld, (c * CH + lane * E + j < V) ? __fsub_rn(mx, v[c][j]) : 0.0f);
+          sd = wave_sum(ld);
+        }
+      }
+      if (g * R + r < a.rows) xent_store(a, row, lane, t, mx, s, li, li1, sd, mi);
+    }
+  }
+}
+
+// Rows of any length: a running maximum per lane, its sums brought along when it grows.  The lane's
+// sum of m - l_v grows by (elements so far) * (the maximum's growth): every term stays >= 0.
+template <class T>
+__global__ __launch_bounds__(LG_THREADS) void k_xent_online(XentArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E, U = LG_ONLINE_U;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const bool sums = a.loss != nullptr || a.stats != nullptr;
+  const bool picks = a.loss != nullptr;
+  const bool smooth = picks && a.eps > 0.0f;
+
+  for (int64_t row = (int64_t)blockIdx.x * LG_WAVES + wave; row < a.rows; row += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t off[1];
+    group_offsets<1>(row, a.rows, a.K, a.sb, a.sk, off);
+    const raw* rowp = static_cast<const raw*>(a.logits) + off[0];
+    const bool aligned = (reinterpret_cast<uintptr_t>(rowp) & 15) == 0;
+    XentTarget t{-2, 0.0f, XENT_TARGET};
+    if (picks) t = xent_target(a, xent_load(a, row));
+    const int ti = __builtin_amdgcn_readfirstlane(t.i);
+    float ml = -INFINITY, zm = 0.0f, ls = 0.0f, li = 0.0f, li1 = 0.0f;   // zm: ml, 0 while ml is -inf
+    float ld = 0.0f, cnt = 0.0f;      // sum of ml - l_v over the lane's cnt elements so far
+    int mi = lane * E;
+    for (int c0 = 0; c0 < V; c0 += U * CH) {
+      Vec16 q[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) q[u] = load_piece<T>(rowp, aligned, c0 + u * CH + lane * E, V);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int e0 = c0 + u * CH + lane * E;
+        float v[E];
+        unpack_piece<T>(q[u], e0, V, v);
+        float cm = ml;
+        int ci = mi;
+#pragma unroll
+        for (int j = 0; j < E; ++j)
+          if (v[j] > cm) {
+            cm = v[j];
+            ci = e0 + j;
+          }
+        if (!sums) {
+          ml = cm;
+          mi = ci;
+          continue;
+        }
+        if (picks) {
+          const int r0 = ti - (c0 + u * CH), r1 = r0 + 1;
+          if (r0 >= 0 && r0 < CH) li = pick_piece<E>(v, r0);
+          if (r1 >= 0 && r1 < CH) li1 = pick_piece<E>(v, r1);
+        }
+        if (cm > ml) {                                       // the lane's maximum grew
+          // while ml is -inf nothing finite is summed: selects, so that 0 * inf and inf - inf cannot arise
+          const bool first = ml == -INFINITY;
+          const float f = first ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(ml, cm), LG_LOG2E));
+          ls = __fmul_rn(ls, f);
+          if (smooth)
+            ld = first ? (cnt > 0.0f ? INFINITY : 0.0f) : __fadd_rn(ld, __fmul_rn(cnt, __fsub_rn(cm, ml)));
+          ml = cm;
+          mi = ci;
+          zm = cm;
+        }
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+          ls = __fadd_rn(ls, exp_shifted(v[j], 1.0f, zm));
+          if (smooth) {
+            const bool real = e0 + j < V;
+            ld = __fadd_rn(ld, (real && ml != -INFINITY) ? __fsub_rn(ml, v[j]) : 0.0f);
+            cnt = __fadd_rn(cnt, real ? 1.0f : 0.0f);
+          }
+        }
+      }
+    }
+    float mx = ml;
+    wave_max(mx, mi);
+    float s = 0.0f, sd = 0.0f;
+    if (sums) {
+      const bool none = ml == -INFINITY;
+      const float f = none ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(ml, mx), LG_LOG2E));
+      s = wave_sum(__fmul_rn(ls, f));
+      if (smooth) {
+        ld = none ? (cnt > 0.0f ? INFINITY : 0.0f) : __fadd_rn(ld, __fmul_rn(cnt, __fsub_rn(mx, ml)));
+        sd = wave_sum(ld);
+      }
+    }
+    xent_store(a, row, lane, t, mx, s, li, li1, sd, mi);
+  }
+}
+
+// grad_v = g (e_v / s - q_v) = fma(g / s, e_v, -g q_v): no sum over the row, so a lane's piece goes
+// from its load to its store.  q_v is eps / V except in bins i and i+1, whose owners are found as in
+// the forward: the chunk and the slot by scalar compares, the lane by one compare per piece.
+struct XentBwdRow {
+  float m, gs;           // gs = g / s
+  float nq, nqi, nqi1;   // -g q_v: elsewhere, in bin i, in bin i+1
+  int i, kind;
+};
+struct XentBwdRaw {
+  XentRaw target;
+  float m, s, g;
+};
+__device__ __forceinline__ XentBwdRaw xent_bwd_load(const XentArgs& a, int64_t row) {
+  return XentBwdRaw{xent_load(a, row), a.stats[2 * row], a.stats[2 * row + 1], a.grad_loss[row]};
+}
+__device__ __forceinline__ XentBwdRow xent_bwd_row(const XentArgs& a, const XentBwdRaw& in) {
+  const XentTarget t = xent_target(a, in.target);
+  XentBwdRow w;
+  const float g = in.g;
+  w.m = in.m;
+  w.gs = __fmul_rn(g, __fdiv_rn(1.0f, in.s));
+  w.nq = -__fmul_rn(g, a.eps_v);
+  w.nqi = -__fmul_rn(g, __fadd_rn(a.eps_v, __fmul_rn(a.keep, __fsub_rn(1.0f, t.f))));
+  w.nqi1 = -__fmul_rn(g, __fadd_rn(a.eps_v, __fmul_rn(a.keep, t.f)));
+  w.i = __builtin_amdgcn_readfirstlane(t.i);
+  w.kind = __builtin_amdgcn_readfirstlane(t.kind);
+  return w;
+}
+
+// The piece as memory holds it.  bf16 goes through the compiler's own float -> bfloat conversion
+// (round to nearest even, NaN stays NaN), which gfx950 has as one packed instruction.
+template <class T>
+__device__ __forceinline__ void pack_piece(const float (&d)[T::EPL], typename T::raw (&o)[T::EPL]) {
+#pragma unroll
+  for (int j = 0; j < T::EPL; ++j) o[j] = T::store(d[j]);
+}
+typedef float F32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 BF16x2 __attribute__((ext_vector_type(2)));
+template <>
+__device__ __forceinline__ void pack_piece<ElemBF16>(const float (&d)[8], uint16_t (&o)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const BF16x2 r = __builtin_convertvector(F32x2{d[j], d[j + 1]}, BF16x2);
+    __builtin_memcpy(&o[j], &r, 4);
+  }
+}
+
+// The gradient of the chunk at `cb` (a wave-uniform element index) of a row that has a target.
+template <class T>
+__device__ __forceinline__ void xent_bwd_piece(const XentBwdRow& w, int cb, int lane, const float (&v)[T::EPL],
+                                               typename T::raw (&o)[T::EPL]) {
+  constexpr int E = T::EPL, CH = 64 * E;
+  float nq[E];
+#pragma unroll
+  for (int j = 0; j < E; ++j) nq[j] = w.nq;
+  const int r0 = w.i - cb, r1 = r0 + 1;
+  if (r0 >= 0 && r0 < CH) {
+    const bool own = lane == r0 / E;
+#pragma unroll
+    for (int j = 0; j < E; ++j) nq[j] = (own && j == (r0 & (E - 1))) ? w.nqi : nq[j];
+  }
+  if (r1 >= 0 && r1 < CH) {
+    const bool own = lane == r1 / E;
+#pragma unroll
+    for (int j = 0; j < E; ++j) nq[j] = (own && j == (r1 & (E - 1))) ? w.nqi1 : nq[j];
+  }
+  float d[E];
+#pragma unroll
+  for (int j = 0; j < E; ++j) d[j] = fmaf(w.gs, exp_shifted(v[j], 1.0f, w.m), nq[j]);   // a -inf logit: e == 0
+  pack_piece<T>(d, o);
+}
+
+// A row without a target: zeros where it is ignored, NaN where its token is out of range.
+template <class T>
+__device__ __forceinline__ void xent_bwd_fill(int kind, typename T::raw (&o)[T::EPL]) {
+  const typename T::raw fill = T::store(kind == XENT_IGNORED ? 0.0f : __builtin_nanf(""));
+#pragma unroll
+  for (int j = 0; j < T::EPL; ++j) o[j] = fill;
+}
+
+// Rows of up to NCH chunks, R of them per wave at a time, held in registers.
+template <class T, int NCH, int R>
+__global__ __launch_bounds__(LG_THREADS) void k_xent_bwd(XentArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const int64_t ngroups = (a.rows + R - 1) / R;
+
+  for (int64_t g = (int64_t)blockIdx.x * LG_WAVES + wave; g < ngroups; g += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t soff[R], doff[R];
+    group_offsets<R>(g * R, a.rows, a.K, a.sb, a.sk, soff);
+    group_offsets<R>(g * R, a.rows, a.gK, a.gsb, a.gsk, doff);
+    XentBwdRaw in[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) in[r] = xent_bwd_load(a, min(g * R + r, a.rows - 1));
+    Vec16 q[R][NCH];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const raw* src = static_cast<const raw*>(a.logits) + soff[r];
+      const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) q[r][c] = load_piece<T>(src, aligned, c * CH + lane * E, V);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (g * R + r >= a.rows) continue;                               // a row the group lacks
+      const XentBwdRow w = xent_bwd_row(a, in[r]);
+      raw* dst = static_cast<raw*>(a.grad) + doff[r];
+      const bool aligned = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int e0 = c * CH + lane * E;
+        if (c > 0 && c * CH >= V) break;
+        raw o[E];
+        if (w.kind == XENT_TARGET) {
+          float v[E];
+          unpack_piece<T>(q[r][c], e0, V, v);
+          xent_bwd_piece<T>(w, c * CH, lane, v, o);
+        } else {
+          xent_bwd_fill<T>(w.kind, o);
+        }
+        store_piece<T>(dst, aligned, e0, V, o);
+      }
+    }
+  }
+}
+
+// Rows of any length, one per wave: one pass, LG_ONLINE_U chunks in flight.
+template <class T>
+__global__ __launch_bounds__(LG_THREADS) void k_xent_bwd_long(XentArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E, U = LG_ONLINE_U;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+
+  for (int64_t row = (int64_t)blockIdx.x * LG_WAVES + wave; row < a.rows; row += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t soff[1], doff[1];
+    group_offsets<1>(row, a.rows, a.K, a.sb, a.sk, soff);
+    group_offsets<1>(row, a.rows, a.gK, a.gsb, a.gsk, doff);
+    const raw* src = static_cast<const raw*>(a.logits) + soff[0];
+    raw* dst = static_cast<raw*>(a.grad) + doff[0];
+    const bool src_al = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    const bool dst_al = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    const XentBwdRow w = xent_bwd_row(a, xent_bwd_load(a, row));
+    for (int c0 = 0; c0 < V; c0 += U * CH) {
+      Vec16 q[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) q[u] = load_piece<T>(src, src_al, c0 + u * CH + lane * E, V);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int e0 = c0 + u * CH + lane * E;
+        raw o[E];
+        if (w.kind == XENT_TARGET) {
+          float v[E];
+          unpack_piece<T>(q[u], e0, V, v);
+          xent_bwd_piece<T>(w, c0 + u * CH, lane, v, o);
+        } else {
+          xent_bwd_fill<T>(w.kind, o);
+        }
+        store_piece<T>(dst, dst_al, e0, V, o);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------ launching --
 // Diagnostic knob: BEAST_DEBUG_LOGITS_ROWS=<1|2|4> rows a wave works on at once (timing tools);
 // default 4 (tests/tools/logits_timing.py).  Results do not depend on it.
@@ -547,8 +1030,8 @@ int64_t resident_workgroups(const Queue& q) {
 
 // Launches K over the rows, R per wave at a time, on the resident workgroups only; with
 // `resident_rows` set it launches nothing and reports how many rows those workgroups hold.
-template <auto K, int R>
-int run_rows(const LogitsArgs& a, const Queue& q, const char* what, int64_t* resident_rows) {
+template <auto K, int R, class Args>
+int run_rows(const Args& a, const Queue& q, const char* what, int64_t* resident_rows) {
   const int64_t wgs = resident_workgroups<K>(q);
   if (resident_rows != nullptr) {
     *resident_rows = wgs * LG_WAVES * R;
@@ -625,6 +1108,53 @@ int check_common(const char* fn, const void* logits, int dtype, int64_t B, int K
   return BEAST_OK;
 }
 
+// The cross-entropy kernels: rows in flight per chunk count are the decode kernels' defaults.
+template <class T>
+int run_xent(bool backward, const XentArgs& a, const Queue& q) {
+  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
+  if (backward) {
+    const char* what = "k_xent_bwd";
+    if (chunks == 1) return run_rows<k_xent_bwd<T, 1, 4>, 4>(a, q, what, nullptr);
+    if (chunks == 2) return run_rows<k_xent_bwd<T, 2, 2>, 2>(a, q, what, nullptr);
+    if (chunks <= LG_MAX_CHUNKS) return run_rows<k_xent_bwd<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, nullptr);
+    return run_rows<k_xent_bwd_long<T>, 1>(a, q, "k_xent_bwd_long", nullptr);
+  }
+  const char* what = "k_xent";
+  if (chunks == 1) return run_rows<k_xent<T, 1, 4>, 4>(a, q, what, nullptr);
+  if (chunks == 2) return run_rows<k_xent<T, 2, 2>, 2>(a, q, what, nullptr);
+  if (chunks <= LG_MAX_CHUNKS) return run_rows<k_xent<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, nullptr);
+  return run_rows<k_xent_online<T>, 1>(a, q, "k_xent_online", nullptr);
+}
+
+int run_xent_typed(int dtype, bool backward, const XentArgs& a, const Queue& q) {
+  switch (dtype) {
+    case BEAST_LOGITS_F32: return run_xent<ElemF32>(backward, a, q);
+    case BEAST_LOGITS_F16: return run_xent<ElemF16>(backward, a, q);
+    default: return run_xent<ElemBF16>(backward, a, q);
+  }
+}
+
+// The checks both cross-entropy directions share (before any HIP call), and the arguments they share.
+int check_xent(const char* fn, const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+               const int64_t* target_tok, const float* target_pos, float smoothing) {
+  BEAST_TRY(check_common(fn, logits, dtype, B, K, V, sb, sk, 1.0f));
+  BEAST_REQUIRE((target_tok != nullptr) != (target_pos != nullptr),
+                "%s: exactly one of target_tok and target_pos must be given", fn);
+  BEAST_REQUIRE(smoothing >= 0.0f && smoothing < 1.0f, "%s: smoothing must lie in [0, 1) (got %g)", fn,
+                (double)smoothing);
+  return BEAST_OK;
+}
+
+XentArgs xent_args(const void* logits, int64_t B, int K, int V, int64_t sb, int64_t sk, const int64_t* target_tok,
+                   const float* target_pos, int64_t tok_offset, int64_t ignore_index, float smoothing) {
+  XentArgs a{};
+  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  a.vm1 = (float)(V - 1);
+  a.tok = target_tok; a.pos = target_pos; a.tok_offset = tok_offset; a.ignore_index = ignore_index;
+  a.eps = smoothing; a.keep = 1.0f - smoothing; a.eps_v = smoothing / (float)V;
+  return a;
+}
+
 }  // namespace
 
 // =================================================================== C-ABI ==
@@ -675,4 +1205,36 @@ extern "C" int64_t beast_logits_resident_rows(int dtype, int V, int backward, vo
   int64_t rows = 0;
   if (const int rc = run_typed(dtype, backward != 0, a, q, &rows)) return rc;
   return rows;
+}
+
+extern "C" int beast_xent_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                               const int64_t* target_tok, const float* target_pos, int64_t tok_offset,
+                               int64_t ignore_index, float smoothing, float* loss_out, float* stats_out,
+                               int64_t* argmax_out, void* queue_stream) {
+  BEAST_TRY(check_xent("beast_xent_rows", logits, dtype, B, K, V, sb, sk, target_tok, target_pos, smoothing));
+  BEAST_REQUIRE(loss_out || stats_out || argmax_out, "beast_xent_rows: no output requested");
+  if (B == 0) return BEAST_OK;
+  XentArgs a = xent_args(logits, B, K, V, sb, sk, target_tok, target_pos, tok_offset, ignore_index, smoothing);
+  a.loss = loss_out; a.stats = stats_out; a.amax = argmax_out;
+  Queue q;
+  if (const int rc = queue_of(queue_stream, q, "beast_xent_rows")) return rc;
+  return run_xent_typed(dtype, false, a, q);
+}
+
+extern "C" int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                                   const int64_t* target_tok, const float* target_pos, int64_t tok_offset,
+                                   int64_t ignore_index, float smoothing, const float* stats,
+                                   const float* grad_loss, void* grad_logits, int64_t gsb, int64_t gsk,
+                                   void* queue_stream) {
+  BEAST_TRY(check_xent("beast_xent_rows_bwd", logits, dtype, B, K, V, sb, sk, target_tok, target_pos, smoothing));
+  BEAST_REQUIRE(stats && grad_loss && grad_logits, "beast_xent_rows_bwd: null pointer");
+  BEAST_REQUIRE(gsb >= 0 && gsk >= V, "beast_xent_rows_bwd: grad_logits rows must not overlap (gsb=%lld, "
+                "gsk=%lld, V=%d)", (long long)gsb, (long long)gsk, V);
+  if (B == 0) return BEAST_OK;
+  XentArgs a = xent_args(logits, B, K, V, sb, sk, target_tok, target_pos, tok_offset, ignore_index, smoothing);
+  a.gK = folded_k(B, K, gsb, gsk);
+  a.stats = const_cast<float*>(stats); a.grad_loss = grad_loss; a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk;
+  Queue q;
+  if (const int rc = queue_of(queue_stream, q, "beast_xent_rows_bwd")) return rc;
+  return run_xent_typed(dtype, true, a, q);
 }

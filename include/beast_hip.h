@@ -41,7 +41,7 @@ extern "C" {
 #define BEAST_E_UNSUPPORTED (-3) /* shape outside the kernels' envelope       */
 #define BEAST_E_WORKSPACE (-4)   /* workspace too small                       */
 
-#define BEAST_ABI_VERSION 1
+#define BEAST_ABI_VERSION 2   /* 2: beast_xent_rows, beast_xent_rows_bwd */
 
 int beast_abi_version(void);
 const char* beast_last_error(void);
@@ -326,6 +326,57 @@ int beast_logits_expect_bwd(const void* logits, int dtype, int64_t B, int K, int
  * resident on the stream's device for this dtype and V: a launch over more rows walks them with a
  * grid stride.  Launches nothing.  Returns the count (> 0) or a negative BEAST_E_* code. */
 int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* hip_stream);
+
+/* Train a discrete head from its logits: the cross-entropy of a token row against a token, or
+ * against the TWO-HOT target of an unquantised normalised coefficient, and its gradient.  The
+ * reference has no counterpart.  The bins are ordinal and affine in the coefficient, so the two
+ * bins around x, weighted 1-f and f, have expectation exactly x: a head trained on that target is
+ * consistent with beast_logits_expect at its optimum.  For one row l[0..V), no temperature:
+ *   m = max_v l_v      e_v = exp(l_v - m)      s = sum_v e_v
+ *   target position u in [0, V-1]:
+ *     from a token t (target_tok, tok_offset subtracted):  u = t
+ *     from a coefficient x (target_pos):  u = clamp(((x + 1) * 0.5) * (V-1), 0, V-1), the three
+ *     roundings in fp32 in this order
+ *   i = min(floor(u), V-2),  f = u - i in [0, 1]
+ *   q_v    = (1-eps) [(1-f) (v == i) + f (v == i+1)] + eps / V          (eps = smoothing)
+ *   loss   = log s + (1-eps) [(1-f) (m - l_i) + f (m - l_{i+1})] + eps (sum_v (m - l_v)) / V
+ *   grad_v = g (e_v / s - q_v)                       (g: the upstream gradient of the row's loss)
+ *   amax   = the lowest v with l_v == m, + tok_offset, as beast_logits_expect
+ * Every term of the loss is >= 0.  A term whose weight is exactly 0 (f == 0, 1-f == 0, eps == 0)
+ * contributes exactly 0 whatever the logit: a -inf logit under a zero weight gives neither NaN nor
+ * inf, under a positive weight it gives +inf loss.  A row whose token equals ignore_index (as
+ * given, before tok_offset is subtracted) or whose coefficient is NaN is ignored: loss exactly 0
+ * and all V gradient elements written as 0.  Any other token outside [tok_offset, tok_offset + V)
+ * gives NaN loss and a NaN gradient row; the target is only compared with v, never an address.  A
+ * row whose logits hold NaN or +inf, or only -inf, has unspecified outputs of its own and
+ * disturbs no other row.
+ *   logits       as beast_logits_expect (dtype, strides, one read per direction, alignment)
+ *   target_tok   [B][K] contiguous int64, or null   } exactly one of the two
+ *   target_pos   [B][K] contiguous fp32, or null    }
+ *   smoothing    in [0, 1)
+ *   loss_out     nullable [B][K]
+ *   stats_out    nullable [B][K][2]  (m, s): the backward's input
+ *   argmax_out   nullable [B][K]     amax + tok_offset
+ *   At least one of the three outputs is non-null.
+ *   grad_loss    [B][K] contiguous;  stats: what the forward wrote for the same logits
+ *   grad_logits  [B][K][V] of `dtype`, element strides gsb >= 0, gsk >= V, V stride 1; every element
+ *                of every row is written and nothing around it.
+ * Rows, lanes and sums are those of beast_logits_expect: a row's outputs are bitwise identical
+ * alone or in any batch, at any alignment, in any grid and from run to run.
+ * queue_stream is the `stream` of the conventions above.  Envelope: 2 <= V <= 65536, else
+ * BEAST_E_UNSUPPORTED; B = 0 returns 0 without a launch. */
+int beast_xent_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                    const int64_t* target_tok, const float* target_pos,
+                    int64_t tok_offset, int64_t ignore_index, float smoothing,
+                    float* loss_out, float* stats_out, int64_t* argmax_out,
+                    void* queue_stream);
+
+int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                        const int64_t* target_tok, const float* target_pos,
+                        int64_t tok_offset, int64_t ignore_index, float smoothing,
+                        const float* stats, const float* grad_loss,
+                        void* grad_logits, int64_t gsb, int64_t gsk,
+                        void* queue_stream);
 
 /* Error statistics of encode -> reconstruct in ONE launch: how well the tokenizer represents the
  * trajectories, and whether the spline fit or the quantiser is to blame.  traj .. dof_src, proj,
