@@ -291,6 +291,26 @@ def _xent_rows(logits, target, tok_offset, ignore_index, smoothing, want_loss, w
     return loss, tokens, stats
 
 
+SAMPLE_MAX_DRAWS = 64      # beast_sample_rows: one draw per lane
+
+
+def _sample_rows(logits, uniforms, temperature, top_k, top_p, tok_offset, want_logprob, want_kept=False):
+    """One launch of ``beast_sample_rows`` on the current stream of the logits' device.  ``logits``
+    is what ``_logits_expect`` takes, ``uniforms`` [S, B, K] contiguous fp32 on the same device.
+    Returns (tokens [S, B, K], logprob or None, kept [B, K] or None)."""
+    B, K, V = logits.shape
+    S = uniforms.shape[0]
+    dev = logits.device
+    tokens = torch.empty((S, B, K), dtype=torch.int64, device=dev)
+    logprob = torch.empty((S, B, K), dtype=torch.float32, device=dev) if want_logprob else None
+    kept = torch.empty((B, K), dtype=torch.int32, device=dev) if want_kept else None
+    if B > 0:
+        _lib.run("beast_sample_rows", logits.data_ptr(), _lib.LOGITS_DTYPES[logits.dtype], B, K, V,
+                 logits.stride(0), logits.stride(1), temperature, top_k, top_p, uniforms.data_ptr(), S, tok_offset,
+                 tokens.data_ptr(), _lib.ptr(logprob), _lib.ptr(kept), _lib.stream_of(dev))
+    return tokens, logprob, kept
+
+
 class _CrossEntropy(torch.autograd.Function):
     """``cross_entropy_from_logits`` per row with a backward: one launch of ``beast_xent_rows`` (loss
     and the row statistics, the greedy tokens too when asked for) forward, one of
@@ -1345,6 +1365,73 @@ class BEASTBsplineTokenizer(TokenizerBase):
         p = self._plan()
         rows = self._logits_rows(logits, p.dev)
         return _logits_expect(rows, 1.0, self._offset(respect_llm_vocab_size), False, True, False)[1]
+
+    @torch.no_grad()
+    def sample_tokens_from_logits(self, logits, *, temperature=1.0, top_k=None, top_p=None, num_samples=None,
+                                  generator=None, uniforms=None, return_log_probs=False,
+                                  respect_llm_vocab_size=True):
+        """Tokens drawn from ``softmax(logits / temperature)`` over the action bins, from one fused
+        launch that reads every row once for all draws: int64 [B, N*D], or
+        [S, B, N*D] when ``num_samples`` = S (1 .. 64) is given, plus the LLM offset exactly as
+        ``encode`` adds it, so they feed ``reconstruct_traj`` unchanged.  Never differentiable.
+
+        ``logits`` is what ``greedy_tokens_from_logits`` takes.  ``top_k`` (None or 0: off) keeps the
+        k largest logits and everything tied with the k-th; ``top_p`` (None or 1: off) then keeps the
+        most probable bins whose renormalised mass reaches ``top_p``, a tie at the edge staying whole
+        (DESIGN.md §8).  With ``return_log_probs`` the fp32 log-probabilities of the drawn tokens
+        under the distribution actually drawn from (after temperature and truncation) come second,
+        in the tokens' shape.
+
+        The draws are inverse-CDF draws of uniforms in [0, 1): by default
+        ``torch.rand((S, B, N*D), generator=generator)`` on the logits' device and the current stream;
+        or the caller's ``uniforms`` of that shape ([B, N*D] or [B, N, D] too when ``num_samples`` is
+        None), cast to fp32 -- the same uniforms give the same tokens, bit for bit."""
+        self._check_logits(logits)
+        temperature = self._check_temperature(temperature)
+        K = self.num_basis * self.num_dof
+        B = logits.shape[0]
+        if top_k is None:
+            top_k = 0
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+            raise ValueError(f"top_k must be None or an integer >= 0; got {top_k!r}")
+        try:
+            p32 = 1.0 if top_p is None else struct.unpack("f", struct.pack("f", float(top_p)))[0]   # as the kernel gets it
+        except (OverflowError, TypeError, ValueError):
+            p32 = float("nan")
+        if not 0.0 < p32 <= 1.0:
+            raise ValueError(f"top_p must be None or lie in (0, 1]; got {top_p!r}")
+        S = 1 if num_samples is None else num_samples
+        if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= SAMPLE_MAX_DRAWS:
+            raise ValueError(f"num_samples must be None or an integer in [1, {SAMPLE_MAX_DRAWS}]; got {num_samples!r}")
+        if uniforms is not None:
+            if generator is not None:
+                raise ValueError("give either generator or uniforms, not both")
+            if not isinstance(uniforms, torch.Tensor) or not uniforms.dtype.is_floating_point:
+                raise ValueError("uniforms must be a floating-point tensor")
+            shapes = {(S, B, K), (S, B, self.num_basis, self.num_dof)}
+            if num_samples is None:
+                shapes |= {(B, K), (B, self.num_basis, self.num_dof)}
+            if tuple(uniforms.shape) not in shapes:
+                raise ValueError(f"uniforms must be [{S}, {B}, {K}]"
+                                 + (f" or [{B}, {K}]" if num_samples is None else "")
+                                 + f"; got {tuple(uniforms.shape)}")
+        truncated = 0 < top_k < self.vocab_size or p32 < 1.0
+        widest = 1024 if logits.dtype in (torch.float32, torch.float64) else 2048
+        if truncated and self.vocab_size > widest:
+            raise NotImplementedError(f"top_k / top_p are supported for vocab_size <= {widest} of {logits.dtype} "
+                                      f"logits (vocab_size={self.vocab_size})")
+        p = self._plan()
+        rows = self._logits_rows(logits, p.dev)
+        if uniforms is None:
+            u = torch.rand((S, B, K), dtype=torch.float32, device=p.dev, generator=generator)
+        else:
+            u = uniforms.to(p.dev, dtype=torch.float32).reshape(S, B, K).contiguous()
+        tokens, logprob, _ = _sample_rows(rows, u, temperature, top_k, p32, self._offset(respect_llm_vocab_size),
+                                          bool(return_log_probs))
+        if num_samples is None:
+            tokens = tokens[0]
+            logprob = logprob[0] if logprob is not None else None
+        return (tokens, logprob) if return_log_probs else tokens
 
     # ===============================================
     #          - training from logits -

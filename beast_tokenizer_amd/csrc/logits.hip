@@ -29,7 +29,9 @@
 //
 // The same machinery carries the training direction (beast_xent_rows, beast_xent_rows_bwd): the
 // cross-entropy of a row against a token or against the two-hot target of an unquantised
-// coefficient, k_xent / k_xent_online and k_xent_bwd / k_xent_bwd_long further down.
+// coefficient, k_xent / k_xent_online and k_xent_bwd / k_xent_bwd_long further down; and the
+// rollout direction (beast_sample_rows): temperature / top-k / top-p draws with their
+// log-probabilities, k_sample / k_sample_long after those.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1002,6 +1004,366 @@ __global__ __launch_bounds__(LG_THREADS) void k_xent_bwd_long(XentArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- sampling kernels --
+// beast_sample_rows on the same row machinery: S inverse-CDF draws from one read of a row, under
+// softmax(l / tau) truncated to the top-k and then the top-p (nucleus) bins.  With
+// e_v = exp(l_v / tau - zmax) as everywhere above:
+//   kept   = {v : l_v >= theta}; theta is the k-th largest logit, raised to the largest logit value
+//            whose upper set still holds p of the top-k survivors' mass (whole tie groups stay)
+//   C_v    = sum of e_w over kept w <= v, in ascending index;  S2 = C_{V-1}
+//   tok_s  = the lowest kept v with e_v > 0 and C_v > u_s S2; the highest kept v with e_v > 0
+//            where rounding leaves none
+//   logprob_s = (l_tok / tau - zmax) - log S2
+// Both thresholds are found on order-preserving integer keys of the raw logits by a bitwise binary
+// search, most significant bit first: the number of keys >= a candidate (ballot + popcount) and the
+// masked wave_sum of e are both monotone in the candidate (a fixed-order fp32 sum of non-negative
+// terms cannot grow when terms are replaced by 0).  The prefix C is built with DPP row shifts and
+// readlanes only: a lane's elements in ascending order, a shift-and-add scan over each 16-lane row,
+// the four row totals in lane order, the chunks one after the other -- no LDS, no atomics, an
+// order fixed by (V, element type).  Lane L's offset is bitwise lane L-1's inclusive value, and a
+// chunk's base is bitwise the last C of the chunk before it.  The draws reuse the row's C in
+// registers; tokens and log-probabilities of the S draws collect in lanes 0 .. S-1 and leave in one
+// store each.  Nothing is addressed by a computed value: a token is a minimum over lane indices.
+struct SampleArgs {
+  const void* logits;
+  int64_t sb, sk;        // element strides of the batch and the token axis
+  int64_t rows;          // B * K
+  int64_t K;             // folded_k of the strides
+  int V;
+  float inv_tau;
+  int top_k;             // 0: no top-k
+  float top_p;           // 1: no top-p
+  const float* u;        // [S][rows]
+  int S;
+  int64_t tok_offset;
+  int64_t* tok;          // [S][rows]
+  float* logprob;        // nullable [S][rows]
+  int32_t* kept;         // nullable [rows]
+};
+
+constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114, DPP_ROW_SHR8 = 0x118;
+
+// An unsigned key with key(a) < key(b) exactly where a < b (-0 and +0 share one key): 32 bits for
+// fp32; for the 16-bit types the 16 bits of the element itself, so the search takes 16 steps.
+template <class T>
+struct SampleKey {
+  static constexpr int BITS = 16;
+};
+template <>
+struct SampleKey<ElemF32> {
+  static constexpr int BITS = 32;
+};
+__device__ __forceinline__ uint32_t ordered_key32(float f) {
+  const uint32_t u = (f == 0.0f) ? 0u : __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+template <class T>
+__device__ __forceinline__ uint32_t sample_key(float f) {
+  return ordered_key32(f);
+}
+template <>
+__device__ __forceinline__ uint32_t sample_key<ElemBF16>(float f) {
+  return ordered_key32(f) >> 16;                 // a bf16 is the upper half of its float
+}
+template <>
+__device__ __forceinline__ uint32_t sample_key<ElemF16>(float f) {
+  const _Float16 h = (_Float16)f;                // exact: f came from an fp16
+  uint16_t b;
+  __builtin_memcpy(&b, &h, 2);
+  const uint32_t u = (f == 0.0f) ? 0u : (uint32_t)b;
+  return (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);
+}
+
+__device__ __forceinline__ int wave_count(bool p) { return __builtin_popcountll(__builtin_amdgcn_ballot_w64(p)); }
+
+// The exclusive prefix of x over the lanes (lane L: x_0 + .. + x_{L-1}, 0 in lane 0), and in
+// `total` the sum over all 64, which is what lane 64 would hold.
+__device__ __forceinline__ float wave_exclusive_scan(float x, int lane, float& total) {
+  x = __fadd_rn(x, dpp_f<DPP_ROW_SHR1>(x));      // lanes a shift has no source for read 0
+  x = __fadd_rn(x, dpp_f<DPP_ROW_SHR2>(x));
+  x = __fadd_rn(x, dpp_f<DPP_ROW_SHR4>(x));
+  x = __fadd_rn(x, dpp_f<DPP_ROW_SHR8>(x));      // inclusive within each row of 16
+  const float r0 = lane_f(x, 15), r1 = lane_f(x, 31), r2 = lane_f(x, 47), r3 = lane_f(x, 63);
+  const float b2 = __fadd_rn(r0, r1), b3 = __fadd_rn(b2, r2);
+  const int rw = lane >> 4;
+  const float rb = rw == 0 ? 0.0f : rw == 1 ? r0 : rw == 2 ? b2 : b3;
+  total = __fadd_rn(b3, r3);
+  return __fadd_rn(rb, dpp_f<DPP_ROW_SHR1>(x));
+}
+
+// One chunk's part of C: e (kept bins only) in, C out with -inf in the bins that cannot be drawn
+// (e == 0), so that a draw is one compare per element; `base` moves on to the chunk's last C.
+template <int E>
+__device__ __forceinline__ void chunk_prefix(const float (&e)[E], int lane, float& base, float (&C)[E]) {
+  float p = 0.0f, loc[E];
+#pragma unroll
+  for (int j = 0; j < E; ++j) {
+    p = __fadd_rn(p, e[j]);
+    loc[j] = p;
+  }
+  float total;
+  const float off = __fadd_rn(base, wave_exclusive_scan(p, lane, total));
+  float last = 0.0f;
+#pragma unroll
+  for (int j = 0; j < E; ++j) {
+    last = __fadd_rn(off, loc[j]);
+    C[j] = (e[j] > 0.0f) ? last : -INFINITY;
+  }
+  base = lane_f(last, 63);
+}
+
+// The highest index a lane holds with e > 0, as the wave's (-1: none).
+__device__ __forceinline__ int wave_max_index(int i) { return -wave_min_index(-i); }
+
+// Rows of up to NCH chunks, R of them per wave at a time, held in registers.  TRUNC: top-k / top-p.
+template <class T, int NCH, int R, bool TRUNC>
+__global__ __launch_bounds__(LG_THREADS) void k_sample(SampleArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const int64_t ngroups = (a.rows + R - 1) / R;
+
+  for (int64_t g = (int64_t)blockIdx.x * LG_WAVES + wave; g < ngroups; g += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t off[R];
+    group_offsets<R>(g * R, a.rows, a.K, a.sb, a.sk, off);
+    float us[R];                                                       // lane s: the row's u_s
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      us[r] = (lane < a.S) ? a.u[(int64_t)lane * a.rows + min(g * R + r, a.rows - 1)] : 0.0f;
+    Vec16 q[R][NCH];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const raw* rowp = static_cast<const raw*>(a.logits) + off[r];
+      const bool aligned = (reinterpret_cast<uintptr_t>(rowp) & 15) == 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) q[r][c] = load_piece<T>(rowp, aligned, c * CH + lane * E, V);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = g * R + r;
+      if (row >= a.rows) continue;                                     // a row the group lacks (wave-uniform)
+      float v[NCH][E];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) unpack_piece<T>(q[r][c], c * CH + lane * E, V, v[c]);
+      float mx = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < E; ++j) mx = fmaxf(mx, v[c][j]);
+      mx = wave_max_value(mx);
+      const float zmax = __fmul_rn(mx, a.inv_tau);
+      float e[NCH][E];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < E; ++j) e[c][j] = exp_shifted(v[c][j], a.inv_tau, zmax);   // padding: 0
+
+      int kept = V;
+      if constexpr (TRUNC) {
+        constexpr int BITS = SampleKey<T>::BITS;
+        uint32_t key[NCH][E];                                          // padding: 0, below every candidate
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+          for (int j = 0; j < E; ++j) key[c][j] = (c * CH + lane * E + j < V) ? sample_key<T>(v[c][j]) : 0u;
+        uint32_t theta = 1;
+        if (a.top_k > 0 && a.top_k < V) {                              // the k-th largest key
+          uint32_t t = 0;
+#pragma unroll 1
+          for (int b = BITS - 1; b >= 0; --b) {
+            const uint32_t cand = t | (1u << b);
+            int n = 0;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+              for (int j = 0; j < E; ++j) n += wave_count(key[c][j] >= cand);
+            t = (n >= a.top_k) ? cand : t;
+          }
+          theta = max(t, 1u);
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int j = 0; j < E; ++j) e[c][j] = (key[c][j] >= theta) ? e[c][j] : 0.0f;
+        }
+        if (a.top_p < 1.0f) {                     // the largest key whose upper set holds p of the mass
+          float ls = 0.0f;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, e[c][j]);
+          const float need = __fmul_rn(a.top_p, wave_sum(ls));
+          uint32_t t = 0;
+#pragma unroll 1
+          for (int b = BITS - 1; b >= 0; --b) {
+            const uint32_t cand = t | (1u << b);
+            float lm = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+              for (int j = 0; j < E; ++j) lm = __fadd_rn(lm, (key[c][j] >= cand) ? e[c][j] : 0.0f);
+            t = (wave_sum(lm) >= need) ? cand : t;
+          }
+          theta = max(t, theta);
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int j = 0; j < E; ++j) e[c][j] = (key[c][j] >= theta) ? e[c][j] : 0.0f;
+        }
+        kept = 0;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+          for (int j = 0; j < E; ++j) kept += wave_count(key[c][j] >= theta);
+      }
+
+      float C[NCH][E];
+      float s2 = 0.0f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) chunk_prefix<E>(e[c], lane, s2, C[c]);
+      const float ln_s2 = __fmul_rn(__builtin_amdgcn_logf(s2), LG_LN2);
+
+      int my_tok = 0;
+      float my_lp = 0.0f;
+      for (int s = 0; s < a.S; ++s) {
+        const float target = __fmul_rn(lane_f(us[r], s), s2);
+        int first = LG_MAX_V;
+#pragma unroll
+        for (int c = NCH - 1; c >= 0; --c)
+#pragma unroll
+          for (int j = E - 1; j >= 0; --j) first = (C[c][j] > target) ? c * CH + lane * E + j : first;
+        int tk = wave_min_index(first);
+        if (tk >= LG_MAX_V) {                                          // rounding (or a NaN) left none
+          int last = -1;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int j = 0; j < E; ++j) last = (e[c][j] > 0.0f) ? c * CH + lane * E + j : last;
+          tk = max(wave_max_index(last), 0);
+        }
+        float lt = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int rel = tk - c * CH;
+          if (rel >= 0 && rel < CH) lt = pick_piece<E>(v[c], rel);
+        }
+        const float lp = __fsub_rn(fmaf(lt, a.inv_tau, -zmax), ln_s2);
+        my_tok = (lane == s) ? tk : my_tok;
+        my_lp = (lane == s) ? lp : my_lp;
+      }
+      if (lane < a.S) {
+        a.tok[(int64_t)lane * a.rows + row] = (int64_t)my_tok + a.tok_offset;
+        if (a.logprob != nullptr) a.logprob[(int64_t)lane * a.rows + row] = my_lp;
+      }
+      if (lane == 0 && a.kept != nullptr) a.kept[row] = kept;
+    }
+  }
+}
+
+// Rows of any length, one per wave, no truncation.  Pass 1: the online maximum and sum.  Pass 2
+// reads the row again (from the L2 pass 1 pulled it through), carries the running prefix chunk by
+// chunk and holds the S targets one per lane: a draw is looked for in the first chunk whose last C
+// exceeds its target.
+template <class T>
+__global__ __launch_bounds__(LG_THREADS) void k_sample_long(SampleArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E, U = LG_ONLINE_U;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+
+  for (int64_t row = (int64_t)blockIdx.x * LG_WAVES + wave; row < a.rows; row += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t off[1];
+    group_offsets<1>(row, a.rows, a.K, a.sb, a.sk, off);
+    const raw* rowp = static_cast<const raw*>(a.logits) + off[0];
+    const bool aligned = (reinterpret_cast<uintptr_t>(rowp) & 15) == 0;
+    const float u = (lane < a.S) ? a.u[(int64_t)lane * a.rows + row] : 0.0f;
+    float ml = -INFINITY, zm = 0.0f, ls = 0.0f;              // zm: ml / tau, 0 while ml is -inf
+    for (int c0 = 0; c0 < V; c0 += U * CH) {
+      Vec16 q[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) q[k] = load_piece<T>(rowp, aligned, c0 + k * CH + lane * E, V);
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        float v[E];
+        unpack_piece<T>(q[k], c0 + k * CH + lane * E, V, v);
+        float cm = ml;
+#pragma unroll
+        for (int j = 0; j < E; ++j) cm = fmaxf(cm, v[j]);
+        if (cm > ml) {                                       // the lane's maximum grew: rescale its sum
+          const float zn = __fmul_rn(cm, a.inv_tau);
+          const float f = (ml == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(zm, zn), LG_LOG2E));
+          ls = __fmul_rn(ls, f);
+          ml = cm;
+          zm = zn;
+        }
+#pragma unroll
+        for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, exp_shifted(v[j], a.inv_tau, zm));
+      }
+    }
+    const float mx = wave_max_value(ml);
+    const float zmax = __fmul_rn(mx, a.inv_tau);
+    const float f = (ml == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(zm, zmax), LG_LOG2E));
+    const float s2 = wave_sum(__fmul_rn(ls, f));
+    const float ln_s2 = __fmul_rn(__builtin_amdgcn_logf(s2), LG_LN2);
+    const float target = __fmul_rn(u, s2);
+
+    bool open = lane < a.S;                                  // this lane's draw has no token yet
+    int my_tok = 0, hi = -1;                                 // hi: the lane's highest index with e > 0
+    float my_lt = 0.0f, hv = 0.0f;                           // hv: the logit there
+    float base = 0.0f;
+    for (int c0 = 0; c0 < V; c0 += U * CH) {
+      Vec16 q[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) q[k] = load_piece<T>(rowp, aligned, c0 + k * CH + lane * E, V);
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const int cb = c0 + k * CH, e0 = cb + lane * E;
+        if (cb >= V) break;                                  // wave-uniform
+        float v[E], e[E], C[E];
+        unpack_piece<T>(q[k], e0, V, v);
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+          e[j] = exp_shifted(v[j], a.inv_tau, zmax);
+          hi = (e[j] > 0.0f) ? e0 + j : hi;
+          hv = (e[j] > 0.0f) ? v[j] : hv;
+        }
+        chunk_prefix<E>(e, lane, base, C);
+        uint64_t m = __builtin_amdgcn_ballot_w64(open && target < base);
+        while (m != 0) {
+          const int s = __builtin_ctzll(m);
+          m &= m - 1;
+          const float t = lane_f(target, s);
+          int first = LG_MAX_V;
+#pragma unroll
+          for (int j = E - 1; j >= 0; --j) first = (C[j] > t) ? e0 + j : first;
+          const int tk = wave_min_index(first);
+          if (tk < LG_MAX_V) {                               // else: a later chunk, or the fallback
+            const float lt = pick_piece<E>(v, tk - cb);
+            const bool mine = lane == s;
+            my_tok = mine ? tk : my_tok;
+            my_lt = mine ? lt : my_lt;
+            open = mine ? false : open;
+          }
+        }
+      }
+    }
+    const int top = wave_max_index(hi);                      // rounding (or a NaN) left some draw open
+    const float top_l = lane_f(hv, (max(top, 0) / E) & 63);
+    if (open) {
+      my_tok = max(top, 0);
+      my_lt = top_l;
+    }
+    if (lane < a.S) {
+      a.tok[(int64_t)lane * a.rows + row] = (int64_t)my_tok + a.tok_offset;
+      if (a.logprob != nullptr)
+        a.logprob[(int64_t)lane * a.rows + row] = __fsub_rn(fmaf(my_lt, a.inv_tau, -zmax), ln_s2);
+    }
+    if (lane == 0 && a.kept != nullptr) a.kept[row] = V;
+  }
+}
+
 // ------------------------------------------------------------------------ launching --
 // Diagnostic knob: BEAST_DEBUG_LOGITS_ROWS=<1|2|4> rows a wave works on at once (timing tools);
 // default 4 (tests/tools/logits_timing.py).  Results do not depend on it.
@@ -1155,9 +1517,58 @@ XentArgs xent_args(const void* logits, int64_t B, int K, int V, int64_t sb, int6
   return a;
 }
 
+// The sampling kernels: rows in flight per chunk count are the decode kernels' defaults; the
+// truncating form only where a truncation is asked for.
+template <class T>
+int run_sample(const SampleArgs& a, bool trunc, const Queue& q) {
+  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
+  const char* what = "k_sample";
+  if (chunks > LG_MAX_CHUNKS) return run_rows<k_sample_long<T>, 1>(a, q, "k_sample_long", nullptr);
+  if (trunc) {
+    if (chunks == 1) return run_rows<k_sample<T, 1, 4, true>, 4>(a, q, what, nullptr);
+    if (chunks == 2) return run_rows<k_sample<T, 2, 2, true>, 2>(a, q, what, nullptr);
+    return run_rows<k_sample<T, LG_MAX_CHUNKS, 1, true>, 1>(a, q, what, nullptr);
+  }
+  if (chunks == 1) return run_rows<k_sample<T, 1, 4, false>, 4>(a, q, what, nullptr);
+  if (chunks == 2) return run_rows<k_sample<T, 2, 2, false>, 2>(a, q, what, nullptr);
+  return run_rows<k_sample<T, LG_MAX_CHUNKS, 1, false>, 1>(a, q, what, nullptr);
+}
+
+constexpr int SAMPLE_MAX_S = 64;      // one draw per lane
+
 }  // namespace
 
 // =================================================================== C-ABI ==
+extern "C" int beast_sample_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                                 float temperature, int top_k, float top_p, const float* uniforms, int S,
+                                 int64_t tok_offset, int64_t* tokens_out, float* logprob_out, int32_t* kept_out,
+                                 void* sample_stream) {
+  BEAST_TRY(check_common("beast_sample_rows", logits, dtype, B, K, V, sb, sk, temperature));
+  BEAST_REQUIRE(top_k >= 0, "beast_sample_rows: top_k must be >= 0 (got %d)", top_k);
+  BEAST_REQUIRE(top_p > 0.0f && top_p <= 1.0f, "beast_sample_rows: top_p must lie in (0, 1] (got %g)", (double)top_p);
+  BEAST_REQUIRE(S >= 1 && S <= SAMPLE_MAX_S, "beast_sample_rows: S must lie in [1, %d] (got %d)", SAMPLE_MAX_S, S);
+  BEAST_REQUIRE(uniforms != nullptr && tokens_out != nullptr, "beast_sample_rows: null pointer");
+  const bool trunc = (top_k > 0 && top_k < V) || top_p < 1.0f;
+  const int epl = dtype == BEAST_LOGITS_F32 ? ElemF32::EPL : ElemF16::EPL;
+  BEAST_REQUIRE_CODE(!trunc || V <= LG_MAX_CHUNKS * 64 * epl, BEAST_E_UNSUPPORTED,
+                     "beast_sample_rows supports top_k / top_p for V <= %d of this dtype (V=%d)",
+                     LG_MAX_CHUNKS * 64 * epl, V);
+  if (B == 0) return BEAST_OK;
+  SampleArgs a{};
+  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  a.inv_tau = (float)(1.0 / (double)temperature);
+  a.top_k = (top_k > 0 && top_k < V) ? top_k : 0; a.top_p = top_p;
+  a.u = uniforms; a.S = S; a.tok_offset = tok_offset;
+  a.tok = tokens_out; a.logprob = logprob_out; a.kept = kept_out;
+  Queue q;
+  if (const int rc = queue_of(sample_stream, q, "beast_sample_rows")) return rc;
+  switch (dtype) {
+    case BEAST_LOGITS_F32: return run_sample<ElemF32>(a, trunc, q);
+    case BEAST_LOGITS_F16: return run_sample<ElemF16>(a, trunc, q);
+    default: return run_sample<ElemBF16>(a, trunc, q);
+  }
+}
+
 extern "C" int beast_logits_expect(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                                    float temperature, int64_t tok_offset, float* mean_out, int64_t* argmax_out,
                                    float* stats_out, void* hip_stream) {

@@ -41,7 +41,7 @@ extern "C" {
 #define BEAST_E_UNSUPPORTED (-3) /* shape outside the kernels' envelope       */
 #define BEAST_E_WORKSPACE (-4)   /* workspace too small                       */
 
-#define BEAST_ABI_VERSION 2   /* 2: beast_xent_rows, beast_xent_rows_bwd */
+#define BEAST_ABI_VERSION 3   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows */
 
 int beast_abi_version(void);
 const char* beast_last_error(void);
@@ -377,6 +377,43 @@ int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, 
                         const float* stats, const float* grad_loss,
                         void* grad_logits, int64_t gsb, int64_t gsk,
                         void* queue_stream);
+
+/* Draw tokens from a discrete head's logits: S inverse-CDF draws per row under
+ * softmax(l / temperature), optionally truncated to the top-k and then the top-p (nucleus) bins,
+ * with the log-probability of every draw.  The reference has no counterpart.  The library holds no
+ * random number generator: the caller owns the uniforms as it owns every other buffer.  For one row
+ * l[0..V), z = l / temperature, zmax = max z, e_v = exp(z_v - zmax):
+ *   top-k (1 <= top_k < V):  theta_k = the k-th largest value of l, counting multiplicity;
+ *     K1 = {v : l_v >= theta_k} -- ties at the k-th value are all kept.  top_k = 0 or >= V: every bin.
+ *   top-p (0 < top_p < 1):  S1 = sum_{K1} e;  theta_p = the largest value t among {l_v : v in K1}
+ *     with sum_{v in K1, l_v >= t} e_v >= top_p S1;  kept = {v in K1 : l_v >= theta_p} -- the
+ *     smallest value-closed set of the most probable bins whose mass reaches top_p; a tie at the
+ *     nucleus' edge stays whole.  top_p = 1: kept = K1.
+ *   draw:  S2 = sum_kept e;  C_v = sum_{w <= v, w in kept} e_w in ascending index;
+ *     tok_s = the lowest kept v with C_v > u_s S2 (the highest kept v with e_v > 0 where rounding
+ *     leaves none);  logprob_s = (z_tok - zmax) - log S2, the log-probability under the distribution
+ *     drawn from;  kept_count = |kept|.
+ * The thresholds compare the raw logits.  A bin with e_v = 0 (a -inf logit) is never drawn; the bin
+ * that holds the maximum is always kept.  A row with NaN or +inf, or only -inf, or a uniform that is
+ * NaN or outside [0, 1), has unspecified outputs of its own, still writes tokens inside
+ * [tok_offset, tok_offset + V) and disturbs no other row.  Nothing is addressed by a computed value.
+ *   logits       as beast_logits_expect (dtype, strides, alignment); the row is read once for all S
+ *                draws (twice, the second time from L2, beyond four chunks)
+ *   uniforms     [S][B][K] contiguous fp32 in [0, 1)
+ *   tokens_out   [S][B][K] int64, tok + tok_offset
+ *   logprob_out  nullable [S][B][K] fp32
+ *   kept_out     nullable [B][K] int32
+ * Rows, lanes and sums are those of beast_logits_expect: a row's outputs are bitwise identical alone
+ * or in any batch, at any alignment, in any grid and from run to run, and draw s depends on u_s only.
+ * sample_stream is the `stream` of the conventions above.  Envelope: 2 <= V <= 65536 and
+ * 1 <= S <= 64; a truncation (1 <= top_k < V or top_p < 1) only for rows of up to four chunks
+ * (V <= 1,024 fp32, V <= 2,048 fp16 / bf16 -- BEAST vocabularies are 256), else BEAST_E_UNSUPPORTED.
+ * temperature finite and > 0, top_k >= 0, 0 < top_p <= 1; B = 0 returns 0 without a launch. */
+int beast_sample_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                      float temperature, int top_k, float top_p,
+                      const float* uniforms, int S, int64_t tok_offset,
+                      int64_t* tokens_out, float* logprob_out, int32_t* kept_out,
+                      void* sample_stream);
 
 /* Error statistics of encode -> reconstruct in ONE launch: how well the tokenizer represents the
  * trajectories, and whether the spline fit or the quantiser is to blame.  traj .. dof_src, proj,
