@@ -21,7 +21,7 @@ BEAST_E_INVALID = -1
 BEAST_E_HIP = -2
 BEAST_E_UNSUPPORTED = -3
 BEAST_E_WORKSPACE = -4
-ABI_VERSION = 3
+ABI_VERSION = 4
 OPT_GENERIC_KERNELS = 1
 OPT_BLOCK_WAVES = 2
 OPT_MERGE_LDS_MIN = 3
@@ -82,6 +82,10 @@ SIGNATURES = {
                                    _vp, _i64, _i64, _vp]),
     "beast_sample_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _i64, _f32, _i32, _f32, _vp, _i32, _i64, _vp, _vp,
                                  _vp, _vp]),
+    "beast_score_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _f32, _vp, _i32,
+                                _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "beast_score_rows_bwd": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _f32, _vp,
+                                    _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "beast_roundtrip_stats_f32": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
                                          _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "beast_colminmax_workspace_bytes": (_sz, [_i64, _i32]),

@@ -342,6 +342,70 @@ class _CrossEntropy(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
+SCORE_STATS = 10           # beast_score_rows: floats per row of stats_out
+
+
+def _score_rows(logits, ref, tokens, temperature, top_k, top_p, tok_offset, ignore_index, want_entropy, want_stats):
+    """One launch of ``beast_score_rows`` on the current stream of the logits' device.  ``logits`` is
+    what ``_logits_expect`` takes, ``ref`` None or a view of the same shape and dtype, ``tokens`` None
+    or [S, B, K] contiguous int64 on the same device.  Returns (logprob [S, B, K], entropy [B, K],
+    kl [B, K], stats), None where not requested."""
+    B, K, V = logits.shape
+    S = 0 if tokens is None else tokens.shape[0]
+    dev = logits.device
+    logprob = torch.empty((S, B, K), dtype=torch.float32, device=dev) if S else None
+    entropy = torch.empty((B, K), dtype=torch.float32, device=dev) if want_entropy else None
+    kl = torch.empty((B, K), dtype=torch.float32, device=dev) if ref is not None else None
+    stats = torch.empty((B, K, SCORE_STATS), dtype=torch.float32, device=dev) if want_stats else None
+    if B > 0:
+        _lib.run("beast_score_rows", logits.data_ptr(), _lib.LOGITS_DTYPES[logits.dtype], B, K, V,
+                 logits.stride(0), logits.stride(1), _lib.ptr(ref), ref.stride(0) if ref is not None else 0,
+                 ref.stride(1) if ref is not None else 0, temperature, top_k, top_p, _lib.ptr(tokens), S, tok_offset,
+                 ignore_index, _lib.ptr(logprob), _lib.ptr(entropy), _lib.ptr(kl), None, _lib.ptr(stats),
+                 _lib.stream_of(dev))
+    return logprob, entropy, kl, stats
+
+
+class _ScoreTokens(torch.autograd.Function):
+    """``score_tokens_from_logits`` with a backward: one launch of ``beast_score_rows`` forward (the
+    log-probabilities, the entropy, the divergence and the row statistics), one of
+    ``beast_score_rows_bwd`` backward for all three upstream gradients.  As with ``_CrossEntropy`` the
+    move, reshape, slice and cast that made ``logits`` lie outside; the reference and the tokens are
+    never differentiable.  Returns (logprob, entropy, kl) with empty tensors for the parts not asked
+    for."""
+
+    @staticmethod
+    def forward(ctx, logits, ref, tokens, consts, want_entropy):
+        logprob, entropy, kl, stats = _score_rows(logits, ref, tokens, *consts, want_entropy, True)
+        ctx.save_for_backward(logits, stats, *(t for t in (ref, tokens) if t is not None))
+        ctx.has = (ref is not None, tokens is not None, want_entropy)
+        ctx.consts = consts
+        empty = logits.new_empty(0, dtype=torch.float32)
+        return tuple(empty if t is None else t for t in (logprob, entropy, kl))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_logprob, grad_entropy, grad_kl):
+        logits, stats, *rest = ctx.saved_tensors
+        has_ref, has_tokens, has_entropy = ctx.has
+        ref = rest.pop(0) if has_ref else None
+        tokens = rest.pop(0) if has_tokens else None
+        B, K, V = logits.shape
+        dev = logits.device
+        grad = torch.empty((B, K, V), dtype=logits.dtype, device=dev)
+        if B > 0:
+            def rows(g, used):                                # a stride-0 expansion becomes rows
+                return g.to(device=dev, dtype=torch.float32).contiguous() if used else None
+            g_lp, g_h, g_kl = rows(grad_logprob, has_tokens), rows(grad_entropy, has_entropy), rows(grad_kl, has_ref)
+            temperature, top_k, top_p, tok_offset, ignore_index = ctx.consts
+            _lib.run("beast_score_rows_bwd", logits.data_ptr(), _lib.LOGITS_DTYPES[logits.dtype], B, K, V,
+                     logits.stride(0), logits.stride(1), _lib.ptr(ref), ref.stride(0) if has_ref else 0,
+                     ref.stride(1) if has_ref else 0, temperature, top_k, top_p, _lib.ptr(tokens),
+                     tokens.shape[0] if has_tokens else 0, tok_offset, ignore_index, stats.data_ptr(),
+                     _lib.ptr(g_lp), _lib.ptr(g_h), _lib.ptr(g_kl), grad.data_ptr(), K * V, V, _lib.stream_of(dev))
+        return grad, None, None, None, None
+
+
 class BEASTBsplineTokenizer(TokenizerBase):
 
     def __init__(self, num_dof=1, num_basis=10, duration=2 * torch.pi, seq_len=50, vocab_size=256,
@@ -1325,6 +1389,21 @@ class BEASTBsplineTokenizer(TokenizerBase):
             raise ValueError(f"temperature must be finite and > 0; got {temperature!r}")
         return t
 
+    @staticmethod
+    def _check_truncation(top_k, top_p):
+        """(top_k, top_p) as the kernels get them: 0 and 1.0 where off, top_p rounded to fp32."""
+        if top_k is None:
+            top_k = 0
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+            raise ValueError(f"top_k must be None or an integer >= 0; got {top_k!r}")
+        try:
+            p32 = 1.0 if top_p is None else struct.unpack("f", struct.pack("f", float(top_p)))[0]   # as the kernel gets it
+        except (OverflowError, TypeError, ValueError):
+            p32 = float("nan")
+        if not 0.0 < p32 <= 1.0:
+            raise ValueError(f"top_p must be None or lie in (0, 1]; got {top_p!r}")
+        return top_k, p32
+
     def expected_params_from_logits(self, logits, *, temperature=1.0, return_tokens=False):
         """The expected normalised coefficients under ``softmax(logits / temperature)``: fp32
         [B, N*D] in (n d) order, the input of ``reconstruct_traj_continuous`` /
@@ -1390,16 +1469,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         temperature = self._check_temperature(temperature)
         K = self.num_basis * self.num_dof
         B = logits.shape[0]
-        if top_k is None:
-            top_k = 0
-        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
-            raise ValueError(f"top_k must be None or an integer >= 0; got {top_k!r}")
-        try:
-            p32 = 1.0 if top_p is None else struct.unpack("f", struct.pack("f", float(top_p)))[0]   # as the kernel gets it
-        except (OverflowError, TypeError, ValueError):
-            p32 = float("nan")
-        if not 0.0 < p32 <= 1.0:
-            raise ValueError(f"top_p must be None or lie in (0, 1]; got {top_p!r}")
+        top_k, p32 = self._check_truncation(top_k, top_p)
         S = 1 if num_samples is None else num_samples
         if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= SAMPLE_MAX_DRAWS:
             raise ValueError(f"num_samples must be None or an integer in [1, {SAMPLE_MAX_DRAWS}]; got {num_samples!r}")
@@ -1432,6 +1502,83 @@ class BEASTBsplineTokenizer(TokenizerBase):
             tokens = tokens[0]
             logprob = logprob[0] if logprob is not None else None
         return (tokens, logprob) if return_log_probs else tokens
+
+    def score_tokens_from_logits(self, logits, tokens=None, *, temperature=1.0, top_k=None, top_p=None,
+                                 ref_logits=None, return_entropy=False, ignore_index=-100,
+                                 respect_llm_vocab_size=True):
+        """The fp32 log-probabilities of given ``tokens`` under exactly the distribution
+        ``sample_tokens_from_logits`` draws from with the same ``temperature`` / ``top_k`` /
+        ``top_p``, from one fused launch over the logits: scoring the tokens that call
+        drew gives the bits of its ``return_log_probs``, so the importance ratio of an on-policy step
+        is exactly 1.
+
+        ``logits`` is what ``sample_tokens_from_logits`` takes.  ``tokens`` is integer, [B, N*D] or
+        [B, N, D], or [S, B, N*D] or [S, B, N, D] with 1 <= S <= 64, carrying the LLM offset as
+        ``encode`` / ``sample_tokens_from_logits`` give them; the result has their shape.  A token equal
+        to ``ignore_index`` scores exactly 0, a token outside the kept set -inf (neither takes part in
+        the backward), any other token outside the action range NaN.  ``tokens`` may be None when the
+        entropy or the divergence is asked for.
+
+        With ``return_entropy`` or ``ref_logits`` the result is the tuple ``(log_probs, entropy, kl)``,
+        parts not asked for None: ``entropy`` [B, N*D] of the truncated, renormalised distribution and
+        ``kl`` [B, N*D] its divergence from ``softmax(ref_logits / temperature)`` over all action bins.
+        ``ref_logits`` has the logits' shape and dtype, is detached and never receives a gradient.
+
+        Differentiable in ``logits`` for all three (one launch of ``beast_score_rows_bwd``, the kept
+        set held constant, the gradient in the logits' own dtype); without ``requires_grad`` or under
+        ``no_grad`` no graph is recorded."""
+        self._check_logits(logits)
+        temperature = self._check_temperature(temperature)
+        N, D = self.num_basis, self.num_dof
+        K = N * D
+        B = logits.shape[0]
+        top_k, p32 = self._check_truncation(top_k, top_p)
+        S = None
+        if tokens is not None:
+            if not isinstance(tokens, torch.Tensor) or tokens.dtype.is_floating_point or tokens.is_complex() \
+                    or tokens.dtype is torch.bool:
+                raise ValueError("tokens must be an integer tensor")
+            shape = tuple(tokens.shape)
+            if shape in ((B, K), (B, N, D)):
+                S = 0                                          # no leading axis
+            elif shape[1:] in ((B, K), (B, N, D)) and 1 <= shape[0] <= SAMPLE_MAX_DRAWS:
+                S = shape[0]
+            else:
+                raise ValueError(f"tokens must be [{B}, {K}], [{B}, {N}, {D}] or the same behind a leading axis of "
+                                 f"1 .. {SAMPLE_MAX_DRAWS} draws; got {shape}")
+        elif not return_entropy and ref_logits is None:
+            raise ValueError("tokens may be None only when return_entropy or ref_logits is given")
+        if ref_logits is not None:
+            if not isinstance(ref_logits, torch.Tensor) or tuple(ref_logits.shape) != tuple(logits.shape):
+                raise ValueError(f"ref_logits must have the logits' shape {tuple(logits.shape)}")
+            if ref_logits.dtype != logits.dtype:
+                raise ValueError(f"ref_logits must have the logits' dtype {logits.dtype}; got {ref_logits.dtype}")
+        ignore_index = int(ignore_index)
+        truncated = 0 < top_k < self.vocab_size or p32 < 1.0
+        widest = 1024 if logits.dtype in (torch.float32, torch.float64) else 2048
+        if truncated and self.vocab_size > widest:
+            raise NotImplementedError(f"top_k / top_p are supported for vocab_size <= {widest} of {logits.dtype} "
+                                      f"logits (vocab_size={self.vocab_size})")
+        p = self._plan()
+        grad = torch.is_grad_enabled() and logits.requires_grad
+        consts = (temperature, top_k, p32, self._offset(respect_llm_vocab_size), ignore_index)
+        with torch.no_grad():
+            tok = None
+            if tokens is not None:
+                tok = tokens.detach().to(p.dev, dtype=torch.int64).reshape(max(S, 1), B, K).contiguous()
+            ref = None if ref_logits is None else self._logits_rows(ref_logits.detach(), p.dev)
+        with torch.set_grad_enabled(grad):
+            rows = self._logits_rows(logits, p.dev)
+            if grad:
+                logprob, entropy, kl = _ScoreTokens.apply(rows, ref, tok, consts, bool(return_entropy))
+                logprob = logprob if tok is not None else None
+                entropy = entropy if return_entropy else None
+                kl = kl if ref is not None else None
+            else:
+                logprob, entropy, kl, _ = _score_rows(rows, ref, tok, *consts, bool(return_entropy), False)
+            if logprob is not None:
+                logprob = logprob.reshape(tokens.shape)
+        return (logprob, entropy, kl) if (return_entropy or ref_logits is not None) else logprob
 
     # ===============================================
     #          - training from logits -

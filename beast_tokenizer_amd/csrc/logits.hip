@@ -31,7 +31,10 @@
 // cross-entropy of a row against a token or against the two-hot target of an unquantised
 // coefficient, k_xent / k_xent_online and k_xent_bwd / k_xent_bwd_long further down; and the
 // rollout direction (beast_sample_rows): temperature / top-k / top-p draws with their
-// log-probabilities, k_sample / k_sample_long after those.
+// log-probabilities, k_sample / k_sample_long after those; and the policy-gradient direction
+// (beast_score_rows, beast_score_rows_bwd): the log-probability of given tokens, the entropy and the
+// divergence from a reference under the sampler's distribution, k_score / k_score_long and
+// k_score_bwd / k_score_bwd_long last.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1115,6 +1118,106 @@ __device__ __forceinline__ void chunk_prefix(const float (&e)[E], int lane, floa
 // The highest index a lane holds with e > 0, as the wave's (-1: none).
 __device__ __forceinline__ int wave_max_index(int i) { return -wave_min_index(-i); }
 
+// The top-k / top-p search of a row held in registers (k_sample, k_score): v the raw logits
+// (padding -inf), e their exp_shifted.  Leaves e == 0 outside the kept set, the elements' keys in
+// `key` (padding: 0, below every candidate) and the threshold key in `theta`: kept = {key >= theta}.
+// Returns |kept|.
+template <class T, int NCH>
+__device__ __forceinline__ int truncate_row(const float (&v)[NCH][T::EPL], float (&e)[NCH][T::EPL], int lane, int V,
+                                            int top_k, float top_p, uint32_t (&key)[NCH][T::EPL], uint32_t& theta) {
+  constexpr int E = T::EPL, CH = 64 * E;
+  constexpr int BITS = SampleKey<T>::BITS;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int j = 0; j < E; ++j) key[c][j] = (c * CH + lane * E + j < V) ? sample_key<T>(v[c][j]) : 0u;
+  theta = 1;
+  if (top_k > 0 && top_k < V) {                                    // the k-th largest key
+    uint32_t t = 0;
+#pragma unroll 1
+    for (int b = BITS - 1; b >= 0; --b) {
+      const uint32_t cand = t | (1u << b);
+      int n = 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < E; ++j) n += wave_count(key[c][j] >= cand);
+      t = (n >= top_k) ? cand : t;
+    }
+    theta = max(t, 1u);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int j = 0; j < E; ++j) e[c][j] = (key[c][j] >= theta) ? e[c][j] : 0.0f;
+  }
+  if (top_p < 1.0f) {                           // the largest key whose upper set holds p of the mass
+    float ls = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, e[c][j]);
+    const float need = __fmul_rn(top_p, wave_sum(ls));
+    uint32_t t = 0;
+#pragma unroll 1
+    for (int b = BITS - 1; b >= 0; --b) {
+      const uint32_t cand = t | (1u << b);
+      float lm = 0.0f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < E; ++j) lm = __fadd_rn(lm, (key[c][j] >= cand) ? e[c][j] : 0.0f);
+      t = (wave_sum(lm) >= need) ? cand : t;
+    }
+    theta = max(t, theta);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int j = 0; j < E; ++j) e[c][j] = (key[c][j] >= theta) ? e[c][j] : 0.0f;
+  }
+  int kept = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int j = 0; j < E; ++j) kept += wave_count(key[c][j] >= theta);
+  return kept;
+}
+
+// A row's online maximum and sum, LG_ONLINE_U chunks in flight (k_sample_long, k_score_long): the
+// exact maximum mx of the raw elements, zmax = mx / tau and s = sum_v exp(l_v / tau - zmax), every
+// lane rescaling its own sum when its maximum grows, the lanes brought to zmax before wave_sum.
+template <class T>
+__device__ __forceinline__ void online_max_sum(const typename T::raw* rowp, bool aligned, int V, int lane,
+                                               float inv_tau, float& mx, float& zmax, float& s) {
+  constexpr int E = T::EPL, CH = 64 * E, U = LG_ONLINE_U;
+  float ml = -INFINITY, zm = 0.0f, ls = 0.0f;              // zm: ml / tau, 0 while ml is -inf
+  for (int c0 = 0; c0 < V; c0 += U * CH) {
+    Vec16 q[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) q[k] = load_piece<T>(rowp, aligned, c0 + k * CH + lane * E, V);
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      float v[E];
+      unpack_piece<T>(q[k], c0 + k * CH + lane * E, V, v);
+      float cm = ml;
+#pragma unroll
+      for (int j = 0; j < E; ++j) cm = fmaxf(cm, v[j]);
+      if (cm > ml) {                                       // the lane's maximum grew: rescale its sum
+        const float zn = __fmul_rn(cm, inv_tau);
+        const float f = (ml == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(zm, zn), LG_LOG2E));
+        ls = __fmul_rn(ls, f);
+        ml = cm;
+        zm = zn;
+      }
+#pragma unroll
+      for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, exp_shifted(v[j], inv_tau, zm));
+    }
+  }
+  mx = wave_max_value(ml);
+  zmax = __fmul_rn(mx, inv_tau);
+  const float f = (ml == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(zm, zmax), LG_LOG2E));
+  s = wave_sum(__fmul_rn(ls, f));
+}
+
 // Rows of up to NCH chunks, R of them per wave at a time, held in registers.  TRUNC: top-k / top-p.
 template <class T, int NCH, int R, bool TRUNC>
 __global__ __launch_bounds__(LG_THREADS) void k_sample(SampleArgs a) {
@@ -1162,60 +1265,8 @@ __global__ __launch_bounds__(LG_THREADS) void k_sample(SampleArgs a) {
 
       int kept = V;
       if constexpr (TRUNC) {
-        constexpr int BITS = SampleKey<T>::BITS;
-        uint32_t key[NCH][E];                                          // padding: 0, below every candidate
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-#pragma unroll
-          for (int j = 0; j < E; ++j) key[c][j] = (c * CH + lane * E + j < V) ? sample_key<T>(v[c][j]) : 0u;
-        uint32_t theta = 1;
-        if (a.top_k > 0 && a.top_k < V) {                              // the k-th largest key
-          uint32_t t = 0;
-#pragma unroll 1
-          for (int b = BITS - 1; b >= 0; --b) {
-            const uint32_t cand = t | (1u << b);
-            int n = 0;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-              for (int j = 0; j < E; ++j) n += wave_count(key[c][j] >= cand);
-            t = (n >= a.top_k) ? cand : t;
-          }
-          theta = max(t, 1u);
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int j = 0; j < E; ++j) e[c][j] = (key[c][j] >= theta) ? e[c][j] : 0.0f;
-        }
-        if (a.top_p < 1.0f) {                     // the largest key whose upper set holds p of the mass
-          float ls = 0.0f;
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, e[c][j]);
-          const float need = __fmul_rn(a.top_p, wave_sum(ls));
-          uint32_t t = 0;
-#pragma unroll 1
-          for (int b = BITS - 1; b >= 0; --b) {
-            const uint32_t cand = t | (1u << b);
-            float lm = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-              for (int j = 0; j < E; ++j) lm = __fadd_rn(lm, (key[c][j] >= cand) ? e[c][j] : 0.0f);
-            t = (wave_sum(lm) >= need) ? cand : t;
-          }
-          theta = max(t, theta);
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int j = 0; j < E; ++j) e[c][j] = (key[c][j] >= theta) ? e[c][j] : 0.0f;
-        }
-        kept = 0;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-#pragma unroll
-          for (int j = 0; j < E; ++j) kept += wave_count(key[c][j] >= theta);
+        uint32_t key[NCH][E], theta;
+        kept = truncate_row<T, NCH>(v, e, lane, V, a.top_k, a.top_p, key, theta);
       }
 
       float C[NCH][E];
@@ -1279,33 +1330,8 @@ __global__ __launch_bounds__(LG_THREADS) void k_sample_long(SampleArgs a) {
     const raw* rowp = static_cast<const raw*>(a.logits) + off[0];
     const bool aligned = (reinterpret_cast<uintptr_t>(rowp) & 15) == 0;
     const float u = (lane < a.S) ? a.u[(int64_t)lane * a.rows + row] : 0.0f;
-    float ml = -INFINITY, zm = 0.0f, ls = 0.0f;              // zm: ml / tau, 0 while ml is -inf
-    for (int c0 = 0; c0 < V; c0 += U * CH) {
-      Vec16 q[U];
-#pragma unroll
-      for (int k = 0; k < U; ++k) q[k] = load_piece<T>(rowp, aligned, c0 + k * CH + lane * E, V);
-#pragma unroll
-      for (int k = 0; k < U; ++k) {
-        float v[E];
-        unpack_piece<T>(q[k], c0 + k * CH + lane * E, V, v);
-        float cm = ml;
-#pragma unroll
-        for (int j = 0; j < E; ++j) cm = fmaxf(cm, v[j]);
-        if (cm > ml) {                                       // the lane's maximum grew: rescale its sum
-          const float zn = __fmul_rn(cm, a.inv_tau);
-          const float f = (ml == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(zm, zn), LG_LOG2E));
-          ls = __fmul_rn(ls, f);
-          ml = cm;
-          zm = zn;
-        }
-#pragma unroll
-        for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, exp_shifted(v[j], a.inv_tau, zm));
-      }
-    }
-    const float mx = wave_max_value(ml);
-    const float zmax = __fmul_rn(mx, a.inv_tau);
-    const float f = (ml == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(zm, zmax), LG_LOG2E));
-    const float s2 = wave_sum(__fmul_rn(ls, f));
+    float mx, zmax, s2;
+    online_max_sum<T>(rowp, aligned, V, lane, a.inv_tau, mx, zmax, s2);
     const float ln_s2 = __fmul_rn(__builtin_amdgcn_logf(s2), LG_LN2);
     const float target = __fmul_rn(u, s2);
 
@@ -1361,6 +1387,510 @@ __global__ __launch_bounds__(LG_THREADS) void k_sample_long(SampleArgs a) {
         a.logprob[(int64_t)lane * a.rows + row] = __fsub_rn(fmaf(my_lt, a.inv_tau, -zmax), ln_s2);
     }
     if (lane == 0 && a.kept != nullptr) a.kept[row] = V;
+  }
+}
+
+// ----------------------------------------------------------------- scoring kernels --
+// beast_score_rows / beast_score_rows_bwd on the same row machinery: the log-probability of S given
+// tokens per row, the entropy and the divergence from a reference row, under exactly the
+// distribution k_sample draws from.  zmax, e, the kept set (truncate_row) and S2 (chunk_prefix's
+// running total in registers, online_max_sum beyond four chunks) are the sampler's, so
+//   log pi_v = (l_v / tau - zmax) - log S2          (kept v;  -inf, pi_v = 0 elsewhere)
+// of a token has the bits of the sampler's logprob_out.  The S tokens sit one per lane; a draw's
+// logit is picked by readlanes of a wave-uniform index (pick_piece), a token is never an address.
+//   H  = -sum_kept pi_v log pi_v        KL = sum_kept pi_v (log pi_v - log rho_v),
+//   log rho_v = (r_v / tau - zr) - log sr over all V bins of the reference row r
+// with every pi_v == 0 term left out by a select.  The forward leaves in stats, per row,
+//   [0] zmax  [1] S2  [2] theta (the lowest kept raw logit; -inf without a truncation)  [3] H  [4] KL
+//   [5] zr  [6] sr  [7] 0  [8], [9] the low and high 32 bits (as bit patterns) of the mask of the
+//   draws that take part in the backward: token in range, not ignored, logprob > -inf
+// so that the backward repeats neither the threshold search nor a row sum:
+//   grad_v = (1/tau) [ sum_s g_s 1[t_s = v] - pi_v (G + g_H (log pi_v + H) - g_KL (log pi_v - log rho_v - KL)) ]
+// with G = sum_s g_s over the draws that take part (one per lane, wave_sum) and pi_v == 0 terms
+// left out by a select: a bin outside the kept set, or with a -inf logit, gets exactly 0.
+constexpr int SCORE_STATS = 10;
+constexpr int SCORE_NO_TOKEN = -1, SCORE_BAD_TOKEN = -2;
+
+struct ScoreArgs {
+  const void* logits;
+  int64_t sb, sk;        // element strides of the batch and the token axis
+  int64_t rows;          // B * K
+  int64_t K;             // folded_k of the strides
+  const void* ref;       // nullable
+  int64_t rsb, rsk, rK;
+  int V;
+  float inv_tau;
+  int top_k;             // 0: no top-k
+  float top_p;           // 1: no top-p
+  const int64_t* tok;    // [S][rows]
+  int S;
+  int64_t tok_offset, ignore_index;
+  float* logprob;        // forward outputs, nullable
+  float* entropy;
+  float* kl;
+  int32_t* kept;
+  float* stats;          // forward: out (nullable); backward: in
+  // backward only
+  const float* g_lp;     // nullable [S][rows]
+  const float* g_h;      // nullable [rows]
+  const float* g_kl;     // nullable [rows]
+  void* grad;
+  int64_t gsb, gsk, gK;
+};
+
+// Lane s: draw s's bin of the row, SCORE_NO_TOKEN where it is ignored (or s >= S), SCORE_BAD_TOKEN
+// where it lies outside [tok_offset, tok_offset + V).
+__device__ __forceinline__ int score_token(const ScoreArgs& a, int64_t row, int lane) {
+  if (lane >= a.S) return SCORE_NO_TOKEN;
+  const int64_t raw = a.tok[(int64_t)lane * a.rows + row];
+  const int64_t tk = raw - a.tok_offset;
+  if (raw == a.ignore_index) return SCORE_NO_TOKEN;
+  if (tk < 0 || tk >= a.V) return SCORE_BAD_TOKEN;
+  return (int)tk;
+}
+
+__device__ __forceinline__ float wave_min_value(float x) { return -wave_max_value(-x); }
+
+__device__ __forceinline__ float ln_of(float s) { return __fmul_rn(__builtin_amdgcn_logf(s), LG_LN2); }
+
+// One element's terms of H and KL: pi log pi and pi (log pi - log rho), 0 where pi == 0.
+struct ScoreTerms {
+  float h, k;
+};
+__device__ __forceinline__ void score_terms(float l, float e, float r, bool with_ref, float inv_tau, float zmax,
+                                            float ln_s2, float inv_s2, float zr, float ln_sr, ScoreTerms& t) {
+  const float p = __fmul_rn(e, inv_s2);
+  const float lp = __fsub_rn(fmaf(l, inv_tau, -zmax), ln_s2);
+  t.h = __fadd_rn(t.h, (p > 0.0f) ? __fmul_rn(p, lp) : 0.0f);
+  if (with_ref) {
+    const float lr = __fsub_rn(fmaf(r, inv_tau, -zr), ln_sr);
+    t.k = __fadd_rn(t.k, (p > 0.0f) ? __fmul_rn(p, __fsub_rn(lp, lr)) : 0.0f);
+  }
+}
+
+// What lane 0 stores for a row, and lanes 0 .. S-1 for its draws.
+__device__ __forceinline__ void score_store(const ScoreArgs& a, int64_t row, int lane, int ti, float my_lp, float zmax,
+                                            float s2, float theta, float H, float KL, float zr, float sr, int kept) {
+  const bool part = ti >= 0 && my_lp > -INFINITY;
+  const uint64_t mask = __builtin_amdgcn_ballot_w64(part);
+  if (lane < a.S && a.logprob != nullptr) a.logprob[(int64_t)lane * a.rows + row] = my_lp;
+  if (lane != 0) return;
+  if (a.entropy != nullptr) a.entropy[row] = H;
+  if (a.kl != nullptr) a.kl[row] = KL;
+  if (a.kept != nullptr) a.kept[row] = kept;
+  if (a.stats != nullptr) {
+    float* st = a.stats + row * SCORE_STATS;
+    st[0] = zmax; st[1] = s2; st[2] = theta; st[3] = H; st[4] = KL; st[5] = zr; st[6] = sr; st[7] = 0.0f;
+    st[8] = __uint_as_float((uint32_t)mask);
+    st[9] = __uint_as_float((uint32_t)(mask >> 32));
+  }
+}
+
+// Rows of up to NCH chunks, R of them per wave at a time, held in registers.  TRUNC: top-k / top-p.
+template <class T, int NCH, int R, bool TRUNC>
+__global__ __launch_bounds__(LG_THREADS) void k_score(ScoreArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const bool with_ref = a.ref != nullptr && (a.kl != nullptr || a.stats != nullptr);
+  const bool sums = with_ref || a.entropy != nullptr || a.stats != nullptr;
+  const bool draws = a.S > 0 && (a.logprob != nullptr || a.stats != nullptr);
+  const int64_t ngroups = (a.rows + R - 1) / R;
+
+  for (int64_t g = (int64_t)blockIdx.x * LG_WAVES + wave; g < ngroups; g += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t off[R], roff[R];
+    group_offsets<R>(g * R, a.rows, a.K, a.sb, a.sk, off);
+    if (with_ref) group_offsets<R>(g * R, a.rows, a.rK, a.rsb, a.rsk, roff);
+    int ti[R];                                                         // lane s: the row's token s
+#pragma unroll
+    for (int r = 0; r < R; ++r) ti[r] = draws ? score_token(a, min(g * R + r, a.rows - 1), lane) : SCORE_NO_TOKEN;
+    Vec16 q[R][NCH], qr[R][NCH];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const raw* rowp = static_cast<const raw*>(a.logits) + off[r];
+      const bool aligned = (reinterpret_cast<uintptr_t>(rowp) & 15) == 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) q[r][c] = load_piece<T>(rowp, aligned, c * CH + lane * E, V);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (with_ref) {
+        const raw* refp = static_cast<const raw*>(a.ref) + roff[r];
+        const bool aligned = (reinterpret_cast<uintptr_t>(refp) & 15) == 0;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) qr[r][c] = load_piece<T>(refp, aligned, c * CH + lane * E, V);
+      } else {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) qr[r][c] = Vec16{0u, 0u, 0u, 0u};
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = g * R + r;
+      if (row >= a.rows) continue;                                     // a row the group lacks (wave-uniform)
+      float v[NCH][E];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) unpack_piece<T>(q[r][c], c * CH + lane * E, V, v[c]);
+      float mx = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < E; ++j) mx = fmaxf(mx, v[c][j]);
+      mx = wave_max_value(mx);
+      const float zmax = __fmul_rn(mx, a.inv_tau);
+      float e[NCH][E];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < E; ++j) e[c][j] = exp_shifted(v[c][j], a.inv_tau, zmax);   // padding: 0
+
+      int kept = V;
+      float theta = -INFINITY;
+      if constexpr (TRUNC) {
+        uint32_t key[NCH][E], tkey;
+        kept = truncate_row<T, NCH>(v, e, lane, V, a.top_k, a.top_p, key, tkey);
+        float lo = INFINITY;                                           // the lowest kept raw logit
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+          for (int j = 0; j < E; ++j) lo = fminf(lo, (key[c][j] >= tkey) ? v[c][j] : INFINITY);
+        theta = wave_min_value(lo);
+      }
+
+      float s2 = 0.0f;                                                 // in the sampler's order
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        float C[E];
+        chunk_prefix<E>(e[c], lane, s2, C);
+      }
+      const float ln_s2 = ln_of(s2);
+
+      float H = 0.0f, KL = 0.0f, zr = 0.0f, sr = 0.0f;
+      if (sums) {
+        const float inv_s2 = __fdiv_rn(1.0f, s2);
+        float rv[NCH][E];
+        float ln_sr = 0.0f;
+        if (with_ref) {
+          float rmx = -INFINITY;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            unpack_piece<T>(qr[r][c], c * CH + lane * E, V, rv[c]);
+#pragma unroll
+            for (int j = 0; j < E; ++j) rmx = fmaxf(rmx, rv[c][j]);
+          }
+          zr = __fmul_rn(wave_max_value(rmx), a.inv_tau);
+          float ls = 0.0f;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int j = 0; j < E; ++j) ls = __fadd_rn(ls, exp_shifted(rv[c][j], a.inv_tau, zr));
+          sr = wave_sum(ls);
+          ln_sr = ln_of(sr);
+        } else {
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int j = 0; j < E; ++j) rv[c][j] = 0.0f;
+        }
+        ScoreTerms t{0.0f, 0.0f};
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+          for (int j = 0; j < E; ++j)
+            score_terms(v[c][j], e[c][j], rv[c][j], with_ref, a.inv_tau, zmax, ln_s2, inv_s2, zr, ln_sr, t);
+        H = -wave_sum(t.h);
+        if (with_ref) KL = wave_sum(t.k);
+      }
+
+      float my_lp = 0.0f;
+      if (draws) {
+        for (int s = 0; s < a.S; ++s) {
+          const int tk = __builtin_amdgcn_readlane(ti[r], s);
+          float lp = 0.0f;
+          if (tk >= 0) {
+            float lt = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+              const int rel = tk - c * CH;
+              if (rel >= 0 && rel < CH) lt = pick_piece<E>(v[c], rel);
+            }
+            lp = (lt >= theta) ? __fsub_rn(fmaf(lt, a.inv_tau, -zmax), ln_s2) : -INFINITY;
+          } else if (tk == SCORE_BAD_TOKEN) {
+            lp = __builtin_nanf("");
+          }
+          my_lp = (lane == s) ? lp : my_lp;
+        }
+      }
+      score_store(a, row, lane, ti[r], my_lp, zmax, s2, theta, H, KL, zr, sr, kept);
+    }
+  }
+}
+
+// Rows of any length, one per wave, no truncation.  Pass 1: the online maximum and sum of the row
+// (and of the reference row).  Pass 2 reads them again (from the L2 pass 1 pulled them through) for
+// the draws' logits and the terms of H and KL.
+template <class T>
+__global__ __launch_bounds__(LG_THREADS) void k_score_long(ScoreArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E, U = LG_ONLINE_U;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const bool with_ref = a.ref != nullptr && (a.kl != nullptr || a.stats != nullptr);
+  const bool sums = with_ref || a.entropy != nullptr || a.stats != nullptr;
+  const bool draws = a.S > 0 && (a.logprob != nullptr || a.stats != nullptr);
+
+  for (int64_t row = (int64_t)blockIdx.x * LG_WAVES + wave; row < a.rows; row += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t off[1], roff[1] = {0};
+    group_offsets<1>(row, a.rows, a.K, a.sb, a.sk, off);
+    if (with_ref) group_offsets<1>(row, a.rows, a.rK, a.rsb, a.rsk, roff);
+    const raw* rowp = static_cast<const raw*>(a.logits) + off[0];
+    const raw* refp = with_ref ? static_cast<const raw*>(a.ref) + roff[0] : rowp;
+    const bool aligned = (reinterpret_cast<uintptr_t>(rowp) & 15) == 0;
+    const bool ref_al = (reinterpret_cast<uintptr_t>(refp) & 15) == 0;
+    const int ti = draws ? score_token(a, row, lane) : SCORE_NO_TOKEN;
+    float mx, zmax, s2;
+    online_max_sum<T>(rowp, aligned, V, lane, a.inv_tau, mx, zmax, s2);
+    const float ln_s2 = ln_of(s2);
+    const float inv_s2 = __fdiv_rn(1.0f, s2);
+    float rmx, zr = 0.0f, sr = 0.0f, ln_sr = 0.0f;
+    if (with_ref) {
+      online_max_sum<T>(refp, ref_al, V, lane, a.inv_tau, rmx, zr, sr);
+      ln_sr = ln_of(sr);
+    }
+    ScoreTerms t{0.0f, 0.0f};
+    float my_lt = 0.0f;
+    if (sums || draws) {
+      for (int c0 = 0; c0 < V; c0 += U * CH) {
+        Vec16 q[U], qr[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) q[k] = load_piece<T>(rowp, aligned, c0 + k * CH + lane * E, V);
+#pragma unroll
+        for (int k = 0; k < U; ++k)
+          qr[k] = with_ref ? load_piece<T>(refp, ref_al, c0 + k * CH + lane * E, V) : Vec16{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          const int cb = c0 + k * CH, e0 = cb + lane * E;
+          if (cb >= V) break;                                          // wave-uniform
+          float v[E], rv[E];
+          unpack_piece<T>(q[k], e0, V, v);
+          unpack_piece<T>(qr[k], e0, V, rv);
+          if (sums) {
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+              score_terms(v[j], exp_shifted(v[j], a.inv_tau, zmax), rv[j], with_ref, a.inv_tau, zmax, ln_s2, inv_s2,
+                          zr, ln_sr, t);
+          }
+          uint64_t m = __builtin_amdgcn_ballot_w64(ti >= cb && ti < cb + CH);
+          while (m != 0) {
+            const int s = __builtin_ctzll(m);
+            m &= m - 1;
+            const float lt = pick_piece<E>(v, __builtin_amdgcn_readlane(ti, s) - cb);
+            my_lt = (lane == s) ? lt : my_lt;
+          }
+        }
+      }
+    }
+    float H = 0.0f, KL = 0.0f;
+    if (sums) {
+      H = -wave_sum(t.h);
+      if (with_ref) KL = wave_sum(t.k);
+    }
+    float my_lp = 0.0f;
+    if (ti >= 0) my_lp = __fsub_rn(fmaf(my_lt, a.inv_tau, -zmax), ln_s2);
+    else if (ti == SCORE_BAD_TOKEN) my_lp = __builtin_nanf("");
+    score_store(a, row, lane, ti, my_lp, zmax, s2, -INFINITY, H, KL, zr, sr, V);
+  }
+}
+
+// What the backward knows of a row before it meets the row's elements.
+struct ScoreBwdRow {
+  float zmax, ln_s2, inv_s2, theta, H, KL, zr, ln_sr;
+  float gh, gk, G;       // the upstream gradients of H and KL; the sum of the draws' that take part
+  float gs;              // lane s: g_s of draw s, 0 where it takes no part
+  uint64_t part;         // the draws that take part
+  bool bad;              // some token is out of range: a NaN row
+};
+__device__ __forceinline__ ScoreBwdRow score_bwd_row(const ScoreArgs& a, int64_t row, int lane, int ti, float g) {
+  const float* st = a.stats + row * SCORE_STATS;
+  ScoreBwdRow w;
+  w.zmax = st[0];
+  const float s2 = st[1];
+  w.ln_s2 = ln_of(s2);
+  w.inv_s2 = __fdiv_rn(1.0f, s2);
+  w.theta = st[2];
+  w.H = st[3];
+  w.KL = st[4];
+  w.zr = st[5];
+  w.ln_sr = ln_of(st[6]);
+  w.gh = a.g_h != nullptr ? a.g_h[row] : 0.0f;
+  w.gk = a.g_kl != nullptr ? a.g_kl[row] : 0.0f;
+  const uint64_t mask = (uint64_t)__float_as_uint(st[8]) | ((uint64_t)__float_as_uint(st[9]) << 32);
+  w.part = mask & __builtin_amdgcn_ballot_w64(ti >= 0);
+  w.gs = ((w.part >> lane) & 1) ? g : 0.0f;
+  w.G = wave_sum(w.gs);
+  w.bad = __builtin_amdgcn_ballot_w64(ti == SCORE_BAD_TOKEN) != 0;
+  return w;
+}
+
+// The gradient of the chunk at `cb` (a wave-uniform element index): the draws whose token lies in it
+// leave the sum of their g_s in the owner's slot; then the softmax terms.  The g_s of one token are
+// summed by wave_sum over their lanes, the others 0 -- the order G is summed in, so that where every
+// draw names one bin sum_s g_s 1[t_s = v] equals G to the bit and pi_v = 1 cancels it exactly.
+template <class T>
+__device__ __forceinline__ void score_bwd_piece(const ScoreArgs& a, const ScoreBwdRow& w, int cb, int lane, int ti,
+                                                const float (&v)[T::EPL], const float (&rv)[T::EPL],
+                                                typename T::raw (&o)[T::EPL]) {
+  constexpr int E = T::EPL, CH = 64 * E;
+  float d[E];
+  if (w.bad) {
+#pragma unroll
+    for (int j = 0; j < E; ++j) d[j] = __builtin_nanf("");
+    pack_piece<T>(d, o);
+    return;
+  }
+  float acc[E];
+#pragma unroll
+  for (int j = 0; j < E; ++j) acc[j] = 0.0f;
+  uint64_t m = w.part & __builtin_amdgcn_ballot_w64(ti >= cb && ti < cb + CH);
+  while (m != 0) {                               // one turn per distinct token of the chunk
+    const int tk = __builtin_amdgcn_readlane(ti, __builtin_ctzll(m));
+    const uint64_t same = w.part & __builtin_amdgcn_ballot_w64(ti == tk);
+    m &= ~same;
+    const float g = wave_sum(((same >> lane) & 1) ? w.gs : 0.0f);
+    const int rel = tk - cb;
+    const bool own = lane == rel / E;
+#pragma unroll
+    for (int j = 0; j < E; ++j) acc[j] = (own && j == (rel & (E - 1))) ? g : acc[j];
+  }
+#pragma unroll
+  for (int j = 0; j < E; ++j) {
+    const float e = (v[j] >= w.theta) ? exp_shifted(v[j], a.inv_tau, w.zmax) : 0.0f;
+    const float p = __fmul_rn(e, w.inv_s2);
+    const float lp = __fsub_rn(fmaf(v[j], a.inv_tau, -w.zmax), w.ln_s2);
+    float qv = w.G;
+    if (a.g_h != nullptr) qv = fmaf(w.gh, __fadd_rn(lp, w.H), qv);
+    if (a.g_kl != nullptr) {
+      const float lr = __fsub_rn(fmaf(rv[j], a.inv_tau, -w.zr), w.ln_sr);
+      qv = fmaf(-w.gk, __fsub_rn(__fsub_rn(lp, lr), w.KL), qv);
+    }
+    const float inner = __fsub_rn(acc[j], (p > 0.0f) ? __fmul_rn(p, qv) : 0.0f);
+    d[j] = __fmul_rn(a.inv_tau, inner);
+  }
+  pack_piece<T>(d, o);
+}
+
+// Rows of up to NCH chunks, R of them per wave at a time, held in registers.
+template <class T, int NCH, int R>
+__global__ __launch_bounds__(LG_THREADS) void k_score_bwd(ScoreArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const bool with_ref = a.g_kl != nullptr;
+  const int64_t ngroups = (a.rows + R - 1) / R;
+
+  for (int64_t g = (int64_t)blockIdx.x * LG_WAVES + wave; g < ngroups; g += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t soff[R], roff[R], doff[R];
+    group_offsets<R>(g * R, a.rows, a.K, a.sb, a.sk, soff);
+    if (with_ref) group_offsets<R>(g * R, a.rows, a.rK, a.rsb, a.rsk, roff);
+    group_offsets<R>(g * R, a.rows, a.gK, a.gsb, a.gsk, doff);
+    int ti[R];
+    float gl[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = min(g * R + r, a.rows - 1);
+      ti[r] = a.g_lp != nullptr ? score_token(a, row, lane) : SCORE_NO_TOKEN;
+      gl[r] = (a.g_lp != nullptr && lane < a.S) ? a.g_lp[(int64_t)lane * a.rows + row] : 0.0f;
+    }
+    Vec16 q[R][NCH], qr[R][NCH];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const raw* src = static_cast<const raw*>(a.logits) + soff[r];
+      const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) q[r][c] = load_piece<T>(src, aligned, c * CH + lane * E, V);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (with_ref) {
+        const raw* refp = static_cast<const raw*>(a.ref) + roff[r];
+        const bool aligned = (reinterpret_cast<uintptr_t>(refp) & 15) == 0;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) qr[r][c] = load_piece<T>(refp, aligned, c * CH + lane * E, V);
+      } else {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) qr[r][c] = Vec16{0u, 0u, 0u, 0u};
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = g * R + r;
+      if (row >= a.rows) continue;                                     // a row the group lacks
+      const ScoreBwdRow w = score_bwd_row(a, row, lane, ti[r], gl[r]);
+      raw* dst = static_cast<raw*>(a.grad) + doff[r];
+      const bool aligned = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int e0 = c * CH + lane * E;
+        if (c > 0 && c * CH >= V) break;
+        float v[E], rv[E];
+        unpack_piece<T>(q[r][c], e0, V, v);
+        unpack_piece<T>(qr[r][c], e0, V, rv);
+        raw o[E];
+        score_bwd_piece<T>(a, w, c * CH, lane, ti[r], v, rv, o);
+        store_piece<T>(dst, aligned, e0, V, o);
+      }
+    }
+  }
+}
+
+// Rows of any length, one per wave: one pass, LG_ONLINE_U chunks in flight.
+template <class T>
+__global__ __launch_bounds__(LG_THREADS) void k_score_bwd_long(ScoreArgs a) {
+  using raw = typename T::raw;
+  constexpr int E = T::EPL, CH = 64 * E, U = LG_ONLINE_U;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int V = a.V;
+  const bool with_ref = a.g_kl != nullptr;
+
+  for (int64_t row = (int64_t)blockIdx.x * LG_WAVES + wave; row < a.rows; row += (int64_t)gridDim.x * LG_WAVES) {
+    int64_t soff[1], roff[1] = {0}, doff[1];
+    group_offsets<1>(row, a.rows, a.K, a.sb, a.sk, soff);
+    if (with_ref) group_offsets<1>(row, a.rows, a.rK, a.rsb, a.rsk, roff);
+    group_offsets<1>(row, a.rows, a.gK, a.gsb, a.gsk, doff);
+    const raw* src = static_cast<const raw*>(a.logits) + soff[0];
+    const raw* refp = with_ref ? static_cast<const raw*>(a.ref) + roff[0] : src;
+    raw* dst = static_cast<raw*>(a.grad) + doff[0];
+    const bool src_al = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    const bool ref_al = (reinterpret_cast<uintptr_t>(refp) & 15) == 0;
+    const bool dst_al = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    const int ti = a.g_lp != nullptr ? score_token(a, row, lane) : SCORE_NO_TOKEN;
+    const float gl = (a.g_lp != nullptr && lane < a.S) ? a.g_lp[(int64_t)lane * a.rows + row] : 0.0f;
+    const ScoreBwdRow w = score_bwd_row(a, row, lane, ti, gl);
+    for (int c0 = 0; c0 < V; c0 += U * CH) {
+      Vec16 q[U], qr[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) q[k] = load_piece<T>(src, src_al, c0 + k * CH + lane * E, V);
+#pragma unroll
+      for (int k = 0; k < U; ++k)
+        qr[k] = with_ref ? load_piece<T>(refp, ref_al, c0 + k * CH + lane * E, V) : Vec16{0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const int cb = c0 + k * CH, e0 = cb + lane * E;
+        if (cb >= V) break;                                            // wave-uniform
+        float v[E], rv[E];
+        unpack_piece<T>(q[k], e0, V, v);
+        unpack_piece<T>(qr[k], e0, V, rv);
+        raw o[E];
+        score_bwd_piece<T>(a, w, cb, lane, ti, v, rv, o);
+        store_piece<T>(dst, dst_al, e0, V, o);
+      }
+    }
   }
 }
 
@@ -1536,6 +2066,67 @@ int run_sample(const SampleArgs& a, bool trunc, const Queue& q) {
 
 constexpr int SAMPLE_MAX_S = 64;      // one draw per lane
 
+// The scoring kernels: rows in flight and the truncating form as for the sampling kernels.
+template <class T>
+int run_score(bool backward, const ScoreArgs& a, bool trunc, const Queue& q) {
+  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
+  if (backward) {
+    const char* what = "k_score_bwd";
+    if (chunks == 1) return run_rows<k_score_bwd<T, 1, 4>, 4>(a, q, what, nullptr);
+    if (chunks == 2) return run_rows<k_score_bwd<T, 2, 2>, 2>(a, q, what, nullptr);
+    if (chunks <= LG_MAX_CHUNKS) return run_rows<k_score_bwd<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, nullptr);
+    return run_rows<k_score_bwd_long<T>, 1>(a, q, "k_score_bwd_long", nullptr);
+  }
+  const char* what = "k_score";
+  if (chunks > LG_MAX_CHUNKS) return run_rows<k_score_long<T>, 1>(a, q, "k_score_long", nullptr);
+  if (trunc) {
+    if (chunks == 1) return run_rows<k_score<T, 1, 4, true>, 4>(a, q, what, nullptr);
+    if (chunks == 2) return run_rows<k_score<T, 2, 2, true>, 2>(a, q, what, nullptr);
+    return run_rows<k_score<T, LG_MAX_CHUNKS, 1, true>, 1>(a, q, what, nullptr);
+  }
+  if (chunks == 1) return run_rows<k_score<T, 1, 4, false>, 4>(a, q, what, nullptr);
+  if (chunks == 2) return run_rows<k_score<T, 2, 2, false>, 2>(a, q, what, nullptr);
+  return run_rows<k_score<T, LG_MAX_CHUNKS, 1, false>, 1>(a, q, what, nullptr);
+}
+
+// The checks both scoring directions share (before any HIP call); `trunc`: a truncation truncates.
+int check_score(const char* fn, const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                const void* ref_logits, int64_t rsb, int64_t rsk, float temperature, int top_k, float top_p,
+                const int64_t* tokens, int S, bool* trunc) {
+  BEAST_TRY(check_common(fn, logits, dtype, B, K, V, sb, sk, temperature));
+  BEAST_REQUIRE(ref_logits == nullptr || (rsb >= 0 && rsk >= 0), "%s: strides must be >= 0 (rsb=%lld, rsk=%lld)", fn,
+                (long long)rsb, (long long)rsk);
+  BEAST_REQUIRE(top_k >= 0, "%s: top_k must be >= 0 (got %d)", fn, top_k);
+  BEAST_REQUIRE(top_p > 0.0f && top_p <= 1.0f, "%s: top_p must lie in (0, 1] (got %g)", fn, (double)top_p);
+  BEAST_REQUIRE(S >= 0 && S <= SAMPLE_MAX_S, "%s: S must lie in [0, %d] (got %d)", fn, SAMPLE_MAX_S, S);
+  BEAST_REQUIRE(S == 0 || tokens != nullptr, "%s: null tokens with S=%d", fn, S);
+  *trunc = (top_k > 0 && top_k < V) || top_p < 1.0f;
+  const int epl = dtype == BEAST_LOGITS_F32 ? ElemF32::EPL : ElemF16::EPL;
+  BEAST_REQUIRE_CODE(!*trunc || V <= LG_MAX_CHUNKS * 64 * epl, BEAST_E_UNSUPPORTED,
+                     "%s supports top_k / top_p for V <= %d of this dtype (V=%d)", fn, LG_MAX_CHUNKS * 64 * epl, V);
+  return BEAST_OK;
+}
+
+ScoreArgs score_args(const void* logits, int64_t B, int K, int V, int64_t sb, int64_t sk, const void* ref_logits,
+                     int64_t rsb, int64_t rsk, float temperature, int top_k, float top_p, const int64_t* tokens,
+                     int S, int64_t tok_offset, int64_t ignore_index) {
+  ScoreArgs a{};
+  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  a.ref = ref_logits; a.rsb = rsb; a.rsk = rsk; a.rK = folded_k(B, K, rsb, rsk);
+  a.inv_tau = (float)(1.0 / (double)temperature);
+  a.top_k = (top_k > 0 && top_k < V) ? top_k : 0; a.top_p = top_p;
+  a.tok = tokens; a.S = S; a.tok_offset = tok_offset; a.ignore_index = ignore_index;
+  return a;
+}
+
+int run_score_typed(int dtype, bool backward, const ScoreArgs& a, bool trunc, const Queue& q) {
+  switch (dtype) {
+    case BEAST_LOGITS_F32: return run_score<ElemF32>(backward, a, trunc, q);
+    case BEAST_LOGITS_F16: return run_score<ElemF16>(backward, a, trunc, q);
+    default: return run_score<ElemBF16>(backward, a, trunc, q);
+  }
+}
+
 }  // namespace
 
 // =================================================================== C-ABI ==
@@ -1567,6 +2158,53 @@ extern "C" int beast_sample_rows(const void* logits, int dtype, int64_t B, int K
     case BEAST_LOGITS_F16: return run_sample<ElemF16>(a, trunc, q);
     default: return run_sample<ElemBF16>(a, trunc, q);
   }
+}
+
+extern "C" int beast_score_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                                const void* ref_logits, int64_t rsb, int64_t rsk, float temperature, int top_k,
+                                float top_p, const int64_t* tokens, int S, int64_t tok_offset, int64_t ignore_index,
+                                float* logprob_out, float* entropy_out, float* kl_out, int32_t* kept_out,
+                                float* stats_out, void* score_stream) {
+  const char* fn = "beast_score_rows";
+  bool trunc = false;
+  BEAST_TRY(check_score(fn, logits, dtype, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
+                        &trunc));
+  BEAST_REQUIRE(logprob_out || entropy_out || kl_out || kept_out || stats_out, "%s: no output requested", fn);
+  BEAST_REQUIRE(logprob_out == nullptr || S >= 1, "%s: logprob_out needs S >= 1", fn);
+  BEAST_REQUIRE(kl_out == nullptr || ref_logits != nullptr, "%s: kl_out needs ref_logits", fn);
+  if (B == 0) return BEAST_OK;
+  ScoreArgs a = score_args(logits, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
+                           tok_offset, ignore_index);
+  a.logprob = logprob_out; a.entropy = entropy_out; a.kl = kl_out; a.kept = kept_out; a.stats = stats_out;
+  Queue q;
+  if (const int rc = queue_of(score_stream, q, fn)) return rc;
+  return run_score_typed(dtype, false, a, trunc, q);
+}
+
+extern "C" int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                                    const void* ref_logits, int64_t rsb, int64_t rsk, float temperature, int top_k,
+                                    float top_p, const int64_t* tokens, int S, int64_t tok_offset,
+                                    int64_t ignore_index, const float* stats, const float* grad_logprob,
+                                    const float* grad_entropy, const float* grad_kl, void* grad_logits, int64_t gsb,
+                                    int64_t gsk, void* score_stream) {
+  const char* fn = "beast_score_rows_bwd";
+  bool trunc = false;
+  BEAST_TRY(check_score(fn, logits, dtype, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
+                        &trunc));
+  BEAST_REQUIRE(stats && grad_logits, "%s: null pointer", fn);
+  BEAST_REQUIRE(grad_logprob || grad_entropy || grad_kl, "%s: no upstream gradient given", fn);
+  BEAST_REQUIRE(grad_logprob == nullptr || S >= 1, "%s: grad_logprob needs S >= 1", fn);
+  BEAST_REQUIRE(grad_kl == nullptr || ref_logits != nullptr, "%s: grad_kl needs ref_logits", fn);
+  BEAST_REQUIRE(gsb >= 0 && gsk >= V, "%s: grad_logits rows must not overlap (gsb=%lld, gsk=%lld, V=%d)", fn,
+                (long long)gsb, (long long)gsk, V);
+  if (B == 0) return BEAST_OK;
+  ScoreArgs a = score_args(logits, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
+                           tok_offset, ignore_index);
+  a.stats = const_cast<float*>(stats); a.g_lp = grad_logprob; a.g_h = grad_entropy; a.g_kl = grad_kl;
+  a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk; a.gK = folded_k(B, K, gsb, gsk);
+  Queue q;
+  if (const int rc = queue_of(score_stream, q, fn)) return rc;
+  return run_score_typed(dtype, true, a, trunc, q);
 }
 
 extern "C" int beast_logits_expect(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,

@@ -41,7 +41,8 @@ extern "C" {
 #define BEAST_E_UNSUPPORTED (-3) /* shape outside the kernels' envelope       */
 #define BEAST_E_WORKSPACE (-4)   /* workspace too small                       */
 
-#define BEAST_ABI_VERSION 3   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows */
+#define BEAST_ABI_VERSION 4   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
+                                 4: beast_score_rows, beast_score_rows_bwd */
 
 int beast_abi_version(void);
 const char* beast_last_error(void);
@@ -414,6 +415,74 @@ int beast_sample_rows(const void* logits, int dtype, int64_t B, int K, int V, in
                       const float* uniforms, int S, int64_t tok_offset,
                       int64_t* tokens_out, float* logprob_out, int32_t* kept_out,
                       void* sample_stream);
+
+/* Score tokens under a discrete head's logits: the log-probability of S given tokens per row, the
+ * entropy of the row's distribution and its divergence from a reference row, with the gradient of
+ * all three.  The reference has no counterpart.  For one row l[0..V), temperature, top_k, top_p:
+ * z, zmax, e_v, the kept set and S2 are EXACTLY those of beast_sample_rows (thresholds on the raw
+ * logits, ties whole, S2 summed in the sampler's order), and
+ *   log pi_v = (z_v - zmax) - log S2 for kept v;  pi_v = 0 and log pi_v = -inf outside the kept set
+ * so the log-probability of a token beast_sample_rows drew has the bits of its logprob_out.
+ *   per draw s < S, token t_s (tok_offset subtracted):  logprob_s = log pi_{t_s}
+ *     a token equal to ignore_index (as given, before the offset is subtracted): exactly 0
+ *     a token outside the kept set, or on a -inf logit: -inf
+ *     any other token outside [tok_offset, tok_offset + V): NaN, and a NaN gradient row
+ *     a draw whose logprob is 0 by ignore_index or -inf takes no part in the backward;
+ *     a token is only compared with v, never an address
+ *   entropy     H  = -sum_kept pi_v log pi_v;  a term with pi_v == 0 is exactly 0 (a select)
+ *   kl          KL = sum_kept pi_v (log pi_v - log rho_v),  rho = softmax(ref / temperature) over
+ *               ALL V bins, never truncated; pi_v == 0 terms are exactly 0; +inf where
+ *               rho_v == 0 < pi_v.  Only with ref_logits.
+ *   kept_count  |kept|
+ *   backward, upstream g_s, g_H, g_KL, the kept set constant; for kept v
+ *     grad_v = (1/temperature) [ sum_s g_s 1[t_s = v] - pi_v sum_s g_s - g_H pi_v (log pi_v + H)
+ *                                + g_KL pi_v (log pi_v - log rho_v - KL) ]
+ *     the sums over s over the draws that take part; grad_v is exactly 0 outside the kept set and
+ *     where pi_v == 0; the reference never receives a gradient.
+ * A row with NaN or +inf, or only -inf, in the logits or the reference has unspecified outputs of
+ * its own, still writes in bounds and disturbs no other row.
+ *   logits        as beast_logits_expect (dtype, strides, alignment); read once per direction
+ *                 (twice forward, the second time from L2, beyond four chunks)
+ *   ref_logits    nullable; same dtype and V, element strides rsb, rsk >= 0, V stride 1
+ *   tokens        [S][B][K] contiguous int64; S = 0: null
+ *   logprob_out   nullable [S][B][K] fp32; needs S >= 1
+ *   entropy_out   nullable [B][K]
+ *   kl_out        nullable [B][K]; needs ref_logits
+ *   kept_out      nullable [B][K] int32
+ *   stats_out     nullable [B][K][10], the backward's input:
+ *                 [0] zmax  [1] S2  [2] the lowest kept raw logit (-inf without a truncation): the
+ *                 backward's kept set is {l_v >= it}, no threshold search  [3] H  [4] KL (0 without
+ *                 ref_logits)  [5], [6] the reference's zmax and sum (0 without)  [7] 0
+ *                 [8], [9] the low and high 32 bits, as bit patterns, of the mask of the draws that
+ *                 take part in the backward
+ *   At least one of the five outputs is non-null.
+ *   stats         what the forward wrote for the same inputs
+ *   grad_logprob  nullable [S][B][K]; needs S >= 1   } at least one of the three;
+ *   grad_entropy  nullable [B][K]                    } the backward reads each logits row once, and
+ *   grad_kl       nullable [B][K]; needs ref_logits  } the reference row only with grad_kl
+ *   grad_logits   [B][K][V] of `dtype`, element strides gsb >= 0, gsk >= V, V stride 1; every element
+ *                 of every row is written and nothing around it.
+ * Rows, lanes and sums are those of beast_logits_expect: a row's outputs are bitwise identical alone
+ * or in any batch, at any alignment, in any grid and from run to run.
+ * score_stream is the `stream` of the conventions above.  Envelope: beast_sample_rows' -- 2 <= V <=
+ * 65536 and 0 <= S <= 64; a truncation (1 <= top_k < V or top_p < 1) only for rows of up to four
+ * chunks (V <= 1,024 fp32, V <= 2,048 fp16 / bf16), else BEAST_E_UNSUPPORTED.  temperature finite
+ * and > 0, top_k >= 0, 0 < top_p <= 1; B = 0 returns 0 without a launch. */
+int beast_score_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                     const void* ref_logits, int64_t rsb, int64_t rsk,
+                     float temperature, int top_k, float top_p,
+                     const int64_t* tokens, int S, int64_t tok_offset, int64_t ignore_index,
+                     float* logprob_out, float* entropy_out, float* kl_out, int32_t* kept_out, float* stats_out,
+                     void* score_stream);
+
+int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
+                         const void* ref_logits, int64_t rsb, int64_t rsk,
+                         float temperature, int top_k, float top_p,
+                         const int64_t* tokens, int S, int64_t tok_offset, int64_t ignore_index,
+                         const float* stats,
+                         const float* grad_logprob, const float* grad_entropy, const float* grad_kl,
+                         void* grad_logits, int64_t gsb, int64_t gsk,
+                         void* score_stream);
 
 /* Error statistics of encode -> reconstruct in ONE launch: how well the tokenizer represents the
  * trajectories, and whether the spline fit or the quantiser is to blame.  traj .. dof_src, proj,
