@@ -157,6 +157,7 @@ class DeviceBasis:
         key = (times.device, "deriv", version, times.numel())
         hit = self._cache.get(key)
         if hit is None:
+            self._drop_stale(times.device, version)
             t = times.reshape(-1)
             hit = torch.zeros((3, 2, t.numel(), self.num_basis), dtype=torch.float32, device=times.device)
             for o in range(3):
@@ -244,6 +245,7 @@ class DeviceBasis:
         hit = self._cache.get(key)
         if hit is not None:
             return hit
+        self._drop_stale(times.device, version)
         T, N = times.numel(), self.num_basis
         phi = torch.zeros((2, T, N), dtype=torch.float32, device=times.device)
         phi[: self.n_kinds] = self.basis_at(times.reshape(-1))
@@ -260,6 +262,17 @@ class DeviceBasis:
         built(times.device)
         self._cache[key] = hit
         return hit
+
+    def _drop_stale(self, device: torch.device, version: int) -> None:
+        """Cache-miss paths only: forget this device's constants of every other grid version, so a
+        loop that calls ``update_times`` per batch keeps one grid's Phi, projections and derivative
+        slabs alive and not all of them.  Kernels of any stream may still be reading the old ones
+        through raw pointers, so the device goes idle before their memory can be handed out again."""
+        stale = [k for k in self._cache if k[0] == device and (k[2] if k[1] == "deriv" else k[1]) != version]
+        if stale:
+            torch.cuda.synchronize(device)
+            for k in stale:
+                del self._cache[k]
 
     def clear(self, device: Optional[torch.device] = None) -> None:
         self._cache = {k: v for k, v in self._cache.items() if device is not None and k[0] != device}
