@@ -8,8 +8,9 @@
 //   codec_device.h       device primitives that know no argument block: FastDiv, LDS-DMA
 //                        staging, st16 store policies, stamps, Geom / Shape / Dims, and the single
 //                        definitions of the arithmetic the kernels must agree on bit for bit
-//                        (wave_sync, lut_fill, lut_quotients, slot_row / slot_values, wave_copy_out;
-//                        the quantiser beast::quantize_bins and beast::dequantize_quotient are common.h's)
+//                        (wave_sync, lut_fill, lut_quotients, fma_quotients, slot_row / slot_values,
+//                        wave_copy_out; the quantiser beast::quantize_bins, beast::dequantize_quotient
+//                        and beast::exact_quotient are common.h's)
 //   codec_encode.h       k_encode (4- / 7-wave tile walk: params = P . y on v_mfma_f32_16x16x4_f32,
 //                        clamp / quantise / (d n)->(n d) / LLM-offset epilogue) and k_encode_v (one
 //                        wave per trajectory, W trajectories per workgroup, no barrier after the
@@ -227,8 +228,9 @@ int launch_rec_v(RecArgs a, const Queue& q) {
   a.ntiles = (a.B + RV_WR - 1) / RV_WR;
   const bool lat = a.B <= 16 * (int64_t)cu_count(q.dev);   // at most one 16-trajectory tile per CU
   mark_launch(launch_mark(FAM_REC_V, RV_WR, RV_WR, KS, false, true, true, lat));
+  const float vm1 = (float)(a.vocab - 1);   // the kernel's own conversion
   const RecVArgs v{a.w_min, a.w_max, a.basis, a.dof_dst, a.init_p, a.init_p_src, a.pos_out, a.tok_offset,
-                   a.init_p_sb, a.vocab, a.lut_n, a.phases};
+                   a.init_p_sb, a.vocab, 1.0f / vm1, a.phases};   // IEEE division: beast::exact_quotient's r
   const unsigned grid = (unsigned)a.ntiles;
   return lat ? launch<k_reconstruct_v<KS, S, LAT_SP>>(grid, RV_WR * 64, L.total, q, "k_reconstruct_v", a.tokens, a.B, 8, v)
              : launch<k_reconstruct_v<KS, S, 0>>(grid, RV_WR * 64, L.total, q, "k_reconstruct_v", a.tokens, a.B, 8, v);

@@ -163,6 +163,27 @@ __device__ __forceinline__ void lut_quotients(const Tok (&t)[NQ], const float* l
   }
 }
 
+// The same quotients without a table: beast::exact_quotient (three VALU) for tokens in [0, qn),
+// where qn is beast::EXACT_QUOTIENT_MAX while vocab <= EXACT_QUOTIENT_MAX and 0 for larger
+// vocabularies; r = RN(1 / vm1) comes from the host.  Every other token (negative, >= qn: tokens
+// are user data) takes the IEEE division behind one branch for all slots, so the bits are
+// lut_quotients' for every input.
+template <int NQ, class Tok>
+__device__ __forceinline__ void fma_quotients(const Tok (&t)[NQ], int qn, float vm1, float r, float (&nrm)[NQ]) {
+  using U = std::make_unsigned_t<Tok>;
+  bool far = false;
+#pragma unroll
+  for (int u = 0; u < NQ; ++u) {
+    far = far | !((U)t[u] < (U)qn);   // 0 <= t < qn: the low dword is the token
+    nrm[u] = beast::exact_quotient((float)(int)t[u], vm1, r);
+  }
+  if (far) {
+#pragma unroll
+    for (int u = 0; u < NQ; ++u)
+      if (!((U)t[u] < (U)qn)) nrm[u] = __fdiv_rn(tok_f32(t[u]), vm1);
+  }
+}
+
 // The accumulators of an MFMA lane (C/D map: rows n = 4 lk + r, r < 4) as quantiser slots: four,
 // or three (Q3, N <= 10): rows 4 lk + 3 of lanes lk < 2 move into slot 2 of lanes lk >= 2 (one
 // v_permlane32_swap), whose own rows there are padding, so 192 slots serve the 140 values.

@@ -41,7 +41,9 @@ struct RecVArgs {
   const int32_t* init_p_src;
   float* pos_out;
   int64_t tok_offset, init_p_sb;
-  int vocab, lut_n, phases;
+  int vocab;
+  float rinv;   // RN(1 / (vocab - 1)), IEEE-divided on the host: beast::exact_quotient's r
+  int phases;
 };
 
 constexpr int LUT_MAX = 4096;   // dequantise LUT tok / (vocab - 1), IEEE-divided once
@@ -327,8 +329,11 @@ __global__ __launch_bounds__(S::W * 64) void k_reconstruct(const void* __restric
 }
 
 // ------------------------------------------------ reconstruct, per-trajectory waves --
-// Latency regime (<= 2 tiles per CU, e.g. the bench's B = 4,096), fixed shapes with
-// num_dof_out == D.  k_reconstruct computes pos^T (rows t, columns (trajectory, DoF)), so a
+// Latency regime, fixed shapes with num_dof_out == D.  The dispatch (rec_v, launch_rec_v in codec.hip)
+// takes this kernel while the batch would give k_reconstruct at most two of its 8-trajectory tiles per
+// CU; its own tiles are 16 trajectories, one wave each, so that is at most one 16-wave tile per CU
+// (B <= 16 CUs, e.g. the bench's B = 4,096), the range in which it stores write-through.
+// k_reconstruct computes pos^T (rows t, columns (trajectory, DoF)), so a
 // lane's accumulators are 4 rows of one output column, 4 * ndo bytes apart: they go through an
 // LDS image, a workgroup barrier and a cooperative store, and HBM sits idle while the whole chip
 // computes.  Here the MFMA computes pos[j] itself: wave j owns trajectory j of the tile, A = W
@@ -346,13 +351,27 @@ __global__ __launch_bounds__(S::W * 64) void k_reconstruct(const void* __restric
 // a.dof_dst), and the LDS addresses of the lane's tokens, bounds, W-image slots and Phi^T operands.
 // Operands that must be zero (rows past T, K-steps past N, rows no DoF maps to) are read from a
 // zeroed LDS region instead of being selected, and slots past the trajectory's tokens write to a
-// spare W-image slot instead of being predicated.  After the barrier the three slots' tokens and
-// bounds are read in one LDS round trip, their LUT entries in a second, and tokens outside the LUT
-// take one IEEE-divide fallback behind the three fast paths.  Bounds and basis still arrive by DMA:
+// spare W-image slot instead of being predicated.  Bounds and basis still arrive by DMA:
 // per-lane global loads of them cost more vector-memory issue time than the chain saves
 // (profiles/r07/codec_chain_ab.txt).
+//
+// Round 11: the lane-only values are no longer computed sixteen times per workgroup.  What hangs on
+// a.dof_dst -- the inverse DoF map and with it the W-image address of each A operand and the
+// kind mask -- is computed by one wave (RV_BUILDER) for its 64 lanes, without the wave's own
+// offset, into a 1 KB LDS table of 16-byte entries; after the barrier every wave reads its lanes'
+// entries in the round trip that fetches its tokens and bounds, and adds its W-image offset.  The
+// dequantise slots map lanes to (n d) without a division (d = lane & 15, n = lane / 16 + 4 u: 192
+// slots for the 140 values), so their offsets, the Phi^T operands' and the output image's stay
+// inline: a handful of VALU each, cheaper than a table read.  The quotient t / (vocab - 1) is
+// beast::exact_quotient (three VALU per slot): no LUT, no fill, no second LDS round trip; tokens
+// outside [0, EXACT_QUOTIENT_MAX) and larger vocabularies take the IEEE division behind one branch.
+// Nothing derived from the bounds or the DoF map outlives the launch.
+#ifndef BEAST_RV_BUILDER
+#define BEAST_RV_BUILDER 3
+#endif
+constexpr int RV_BUILDER = BEAST_RV_BUILDER < RV_WR ? BEAST_RV_BUILDER : RV_WR - 1;   // the wave that fills the lane table
 struct RvSmem {
-  int tok, wlo, whi, phi, zero, lut, wimg, img, total;
+  int tok, wlo, whi, phi, zero, tab, wimg, img, total;
 };
 template <class S>
 __host__ __device__ constexpr int rv_zero_bytes(int nkinds) {   // every Phi^T operand offset, from a zero base
@@ -368,10 +387,16 @@ __host__ __device__ constexpr RvSmem rv_smem(int nkinds) {
   s.whi = o;  o += round_up(per * 4, 256);
   s.phi = o;  o += round_up(nkinds * S::T * S::N * 4, 1024);
   s.zero = o; o += rv_zero_bytes<S>(nkinds);
-  s.lut = o;  o += round_up(LUT_MAX * 4, 16);
-  s.wimg = o; o += round_up(RV_WR * (per + 4) * 4, 16);        // W[j][d][n] (d n) + a spare slot, one per wave
+  s.tab = o;  o += 64 * 16;                                      // lane table: {wa[0..2], am[0]} per lane
+  s.wimg = o; o += round_up(RV_WR * (per + 4) * 4, 16);        // W[j][d][n] (d n) + a spare and a zero slot, one per wave
   s.img = o;  o += RV_WR * round_up(S::T * S::D * 4, 16);        // pos[j] [T][D], one per wave
-  s.total = o;
+  // A 16-wave tile keeps a CU to itself, as it did while the LUT made it larger than half the CU's
+  // 160 KB: without the LUT the layout is 78 KB and two tiles could share a CU while others idle.
+  // The request is padded past 80 KB so that placement stays what every measurement of this kernel
+  // was made with; nothing uses the pad.  Unpadded, 3 of 26 runs of the B = 4,096 step came out at
+  // 9.0 - 13.5 us against 8.6; padded 0 of 20, the parent 0 of 26: too few to name the cause
+  // (profiles/r11/reconstruct_lane_table_ab.txt).
+  s.total = (RV_WR == 16 && o <= 84 * 1024) ? 84 * 1024 : o;
   return s;
 }
 
@@ -387,15 +412,17 @@ __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __rest
   constexpr int nkinds = NJ < D ? 2 : 1;
   constexpr RvSmem L = rv_smem<S>(nkinds);
   constexpr int RV_IMG = round_up(T * D * 4, 16) / 4;   // floats per wave's output image
-  constexpr int WIMG = per + 4;                         // floats per wave's W image; [per] is the spare slot
-  constexpr int NU = (per + 63) / 64;                   // dequantise slots per lane
+  constexpr int WIMG = per + 4;                         // floats per wave's W image; [per] spare, [per + 1] zero
+  constexpr int DP = D <= 4 ? 4 : D <= 8 ? 8 : 16;      // lanes per coefficient row of the dequantise slots
+  constexpr int RPS = 64 / DP;                          // coefficient rows per slot
+  constexpr int NU = (N + RPS - 1) / RPS;               // dequantise slots per lane
   constexpr int NTT = (T + 15) / 16;                    // 16-row tiles of the output
   static_assert((T * D) % 4 == 0, "per-trajectory reconstruct: whole 16-byte rows");
+  static_assert(KS <= 3, "per-trajectory reconstruct: a lane-table entry holds three A-operand offsets and a mask");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* wlo = reinterpret_cast<float*>(smem + L.wlo);
   float* whi = reinterpret_cast<float*>(smem + L.whi);
   float* phi = reinterpret_cast<float*>(smem + L.phi);
-  float* lut = reinterpret_cast<float*>(smem + L.lut);
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int64_t b0 = (int64_t)blockIdx.x * RV_WR;
   STAMP(1, 0);
@@ -410,45 +437,31 @@ __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __rest
     if ((pbytes & 15) == 0 && (((uintptr_t)a.basis) & 15) == 0) dma16<NT>(phi, a.basis, pbytes >> 4);
     else dma4<NT>(phi, a.basis, pbytes >> 2);
   }
+  STAMP(1, 13);
   const float vm1 = (float)(a.vocab - 1);
-  lut_fill(lut, a.lut_n, vm1, NT);
+  const int qn = a.vocab <= beast::EXACT_QUOTIENT_MAX ? beast::EXACT_QUOTIENT_MAX : 0;
   for (int i = tid; i < rv_zero_bytes<S>(nkinds) / 4; i += NT) reinterpret_cast<float*>(smem + L.zero)[i] = 0.0f;
   STAMP(1, 12);
-  // ---- lane-only values, while the DMA is in flight
   const int j = wave;
   const int nb = (int)min<int64_t>(RV_WR, B - b0);
-  // dequantise slot u: token e = 64 u + lane of the trajectory, (n d) order -> W column k = d N + n
-  int te[NU], kb[NU], wk[NU];   // byte offsets: the token, its column in a bounds array, its W-image slot
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int e = u * 64 + lane, ec = min(e, per - 1);
-    const int n = ec / D, d = ec - n * D, k = d * N + n;
-    te[u] = L.tok + (j * per + ec) * 8;
-    kb[u] = k * 4;
-    wk[u] = L.wimg + (j * WIMG + (e < per ? k : per)) * 4;
-    pin(te[u]); pin(kb[u]); pin(wk[u]);
-  }
-  // A = W: row c = lane & 15 is output column c, i.e. DoF d with dof_dst[d] == c; K-step s holds
-  // n = kk * KS + s (k_reconstruct's mapping), zero past N, past D and for the other kind
   const int c = lane & 15, kk = lane >> 4;
-  int dsrc = -1;
-  const_i32* dof_dst = (const_i32*)a.dof_dst;
+  // ---- lane-only values that are cheaper inline than read from a table, while the DMA is in flight
+  // the wave's zero slot: A operands that must be zero are read from it
+  *reinterpret_cast<float*>(smem + L.wimg + (j * WIMG + per + 1) * 4) = 0.0f;
+  // dequantise slot u: DoF d = lane % DP, coefficient n = lane / DP + RPS u -> token (n d), W column
+  // k = d N + n; slots outside the trajectory read its token 0 and write the spare W-image slot
+  int te[NU], kb[NU], wk[NU];   // byte offsets: the token, its column in a bounds array, its W-image slot
+  {
+    const int sd = lane & (DP - 1), sn = lane / DP;
 #pragma unroll
-  for (int d = 0; d < D; ++d) dsrc = dof_dst[d] == c ? d : dsrc;
-  const bool row_ok = dsrc >= 0;
-  const int dd = row_ok ? dsrc : 0;
-  int wa[KS];            // byte offset of W[dd][n], or of a zero
-  unsigned am[nkinds];   // ~0 where the row belongs to the kind's chain
-#pragma unroll
-  for (int s2 = 0; s2 < KS; ++s2) {
-    const int n = kk * KS + s2;
-    wa[s2] = (row_ok && n < N) ? L.wimg + (j * WIMG + dd * N + n) * 4 : L.zero;
-    pin(wa[s2]);
-  }
-#pragma unroll
-  for (int kd = 0; kd < nkinds; ++kd) {
-    am[kd] = (nkinds == 1 || ((dd < NJ) == (kd == 0))) ? ~0u : 0u;
-    pin(am[kd]);
+    for (int u = 0; u < NU; ++u) {
+      const int n = sn + RPS * u;
+      const bool ok = sd < D && n < N;
+      te[u] = L.tok + (j * per + (ok ? n * D + sd : 0)) * 8;
+      kb[u] = ok ? (sd * N + n) * 4 : 0;
+      wk[u] = L.wimg + (j * WIMG + (ok ? sd * N + n : per)) * 4;
+      pin(te[u]); pin(kb[u]); pin(wk[u]);
+    }
   }
   // B = Phi_kind^T: column t = 16 tt + c, K-step s: n = kk * KS + s.  pa: the whole row tiles
   // (t < T for every c), pt: the last, partial one; kind and tile are constant offsets
@@ -463,12 +476,35 @@ __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __rest
   // this lane's part of pos[j]: row t = 16 tt + c, columns 4 kk .. 4 kk + 3
   int ia = L.img + (j * RV_IMG + c * D + 4 * kk) * 4;
   pin(ia);
-  __syncthreads();   // every DMA, the LUT and the zeros are in place
+  STAMP(1, 14);
+  // ---- the lane table, by one wave: A = W, row c = lane & 15 is output column c, i.e. DoF d with
+  //      dof_dst[d] == c; K-step s holds n = kk * KS + s (k_reconstruct's mapping), zero past N, past D
+  //      and for the other kind.  Entry: the byte offsets of W[dd][n] in a wave's W image (or of its
+  //      zero slot), s < KS, and the mask that is ~0 where the row belongs to the joint kind's chain.
+  if (wave == RV_BUILDER) {
+    int dsrc = -1;
+    const_i32* dof_dst = (const_i32*)a.dof_dst;
+#pragma unroll
+    for (int d = 0; d < D; ++d) dsrc = dof_dst[d] == c ? d : dsrc;
+    const bool row_ok = dsrc >= 0;
+    const int dd = row_ok ? dsrc : 0;
+    int ent[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int s2 = 0; s2 < KS; ++s2) {
+      const int n = kk * KS + s2;
+      ent[s2] = L.wimg + ((row_ok && n < N) ? dd * N + n : per + 1) * 4;
+    }
+    ent[3] = (nkinds == 1 || dd < NJ) ? -1 : 0;
+    *reinterpret_cast<int4*>(smem + L.tab + lane * 16) = make_int4(ent[0], ent[1], ent[2], ent[3]);
+  }
+  STAMP(1, 15);
+  STAMP(1, 1);
+  __syncthreads();   // every DMA, the lane table and the zeros are in place
   STAMP(1, 2);
   if (j >= nb) return;   // no barrier follows
   // ---- W[j][d][n] of this wave's trajectory (bit-exact discrete_to_continuous, init_p for n = 0 of
-  //      the joint DoFs: reference :505-510) into its LDS image: the slots' tokens and bounds in one
-  //      LDS round trip, their LUT entries in a second
+  //      the joint DoFs: reference :505-510) into its LDS image: the slots' tokens and bounds and
+  //      the lane's table entry in one LDS round trip
   long long tv[NU];
   float lo[NU], hi[NU];
 #pragma unroll
@@ -477,14 +513,24 @@ __global__ __launch_bounds__(RV_WR * 64) void k_reconstruct_v(const void* __rest
     lo[u] = *reinterpret_cast<const float*>(smem + L.wlo + kb[u]);
     hi[u] = *reinterpret_cast<const float*>(smem + L.whi + kb[u]);
   }
+  const int4 ent = *reinterpret_cast<const int4*>(smem + L.tab + lane * 16);
   float nrm[NU];
-  lut_quotients(tv, lut, a.lut_n, vm1, nrm);
+  fma_quotients(tv, qn, vm1, a.rinv, nrm);
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     float w = beast::dequantize_quotient(nrm[u], lo[u], hi[u]);
     if (u == 0 && a.init_p != nullptr && lane < NJ)   // slot 0 of lanes d < NJ is n = 0 of the joint DoFs
       w = a.init_p[(b0 + j) * a.init_p_sb + a.init_p_src[lane]];
     *reinterpret_cast<float*>(smem + wk[u]) = w;
+  }
+  int wa[KS];            // byte offset of W[dd][n], or of the wave's zero slot
+  unsigned am[nkinds];   // ~0 where the row belongs to the kind's chain
+  {
+    const int et[3] = {ent.x, ent.y, ent.z};
+#pragma unroll
+    for (int s2 = 0; s2 < KS; ++s2) wa[s2] = et[s2] + j * WIMG * 4;
+#pragma unroll
+    for (int kd = 0; kd < nkinds; ++kd) am[kd] = kd == 0 ? (unsigned)ent.w : ~(unsigned)ent.w;
   }
   wave_sync();
   STAMP(1, 3);

@@ -121,6 +121,18 @@ __device__ __forceinline__ long long widen_bin(int bin, unsigned long long offse
 __device__ __forceinline__ float dequantize_quotient(float n, float lo, float hi) {
   return clamp_t(__fadd_rn(__fmul_rn(n, __fsub_rn(hi, lo)), lo), lo, hi);
 }
+// The quotient t / vm1 without the division: RN(t / vm1) exactly, for integers 0 <= t <
+// EXACT_QUOTIENT_MAX and vm1 = vocab - 1 with 2 <= vocab <= EXACT_QUOTIENT_MAX.  r = RN(1 / vm1),
+// IEEE-divided on the host.  q0 is within an ulp of the quotient, e = t - q0 vm1 is exact in fp32,
+// and one more fma lands on the correctly rounded quotient (tests/test_exact_quotient.py checks
+// every pair in exact integer arithmetic).  Outside that domain callers take __fdiv_rn.
+constexpr int EXACT_QUOTIENT_MAX = 4096;
+__device__ __forceinline__ float exact_quotient(float t, float vm1, float r) {
+  const float q0 = __fmul_rn(t, r);
+  const float e = __fmaf_rn(-q0, vm1, t);
+  return __fmaf_rn(e, r, q0);
+}
+
 __device__ __forceinline__ float dequantize_one(long long tok, float lo, float hi, float vm1) {
   return dequantize_quotient(__fdiv_rn((float)tok, vm1), lo, hi);
 }

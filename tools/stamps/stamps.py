@@ -18,7 +18,10 @@ NW = 16   # stamp slots per kernel (waves per workgroup <= 16; g_stamps[2][16][1
 ENC = ["start", "issued", "landed", "mfma_done", "pb_ready", "params_stored", "tokens_stored", "drained", "acc_ready",
        "y_dma", "p_dma", "small_dma", "t2_landed", "t2_mfma_done", "t2_tokens_stored"]
 REC = ["start", "issued", "landed", "decoded", "w_ready", "mfma_done", "ob_ready", "stored", "drained",
-       "tok_dma", "small_dma", "phi_loads", "lut"]
+       "tok_dma", "small_dma", "phi_loads", "lut",
+       # k_reconstruct_v's prologue: every DMA issued, the inline lane-only values done, the lane table written
+       # ("lut" is its zero fill; "issued" its arrival at the tile barrier)
+       "dma_issued", "lane_done", "table_done"]
 
 
 def build():
