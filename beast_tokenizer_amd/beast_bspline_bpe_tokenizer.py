@@ -257,6 +257,17 @@ class BEASTBsplineBPETokenizer(BEASTBsplineTokenizer):
         out = (self._discrete_to_bpe(mp_tokens, as_tensors=return_tensors), params)
         return out + (mp_tokens,) if return_mp_tokens else out
 
+    def encode_windows(self, frames: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor,
+                       update_bounds: bool = False, *, return_mp_tokens: bool = False, return_tensors: bool = False,
+                       process_group=None) -> tuple:
+        """``encode`` of the windows of a flat frame buffer
+        (:meth:`BEASTBsplineTokenizer.encode_windows`): the BPE ids of those MP tokens."""
+        mp_tokens, params = BEASTBsplineTokenizer.encode_windows(self, frames, starts, ends, update_bounds,
+                                                                 respect_llm_vocab_size=False,
+                                                                 process_group=process_group)
+        out = (self._discrete_to_bpe(mp_tokens, as_tensors=return_tensors), params)
+        return out + (mp_tokens,) if return_mp_tokens else out
+
     def bpe_to_mp_tokens(self, tokens: Iterable[TokenLike]) -> torch.Tensor:
         """Convert BPE tokens back to discrete BEAST bins."""
         return self._bpe_to_discrete(tokens)

@@ -135,7 +135,7 @@ class _Plan:
 
     __slots__ = ("dev", "idx", "version", "wmin", "wmax", "keep", "T", "min_din", "dkey", "pinned",
                  "p_phi", "p_proj", "p_src", "p_dst", "p_wmn", "p_wmx", "enc", "rec", "fast", "fast_addr",
-                 "fast_enc", "fast_rec", "llm", "off")
+                 "fast_enc", "fast_rec", "llm", "off", "enc_win")
 
     def __init__(self, tok: "BEASTBsplineTokenizer", dev: torch.device):
         lib = _lib.load()
@@ -157,6 +157,7 @@ class _Plan:
         self.p_src, self.p_dst = src.data_ptr(), dst.data_ptr()
         self.p_wmn, self.p_wmx = wmn.data_ptr(), wmx.data_ptr()
         self.enc, self.rec = lib.beast_encode_f32, lib.beast_reconstruct_f32
+        self.enc_win = lib.beast_encode_windows_f32
         fp = _fastpath()
         self.fast = self.fast_addr = self.fast_enc = self.fast_rec = None
         if fp is not None and not tok._conditioned:
@@ -404,6 +405,40 @@ class _ScoreTokens(torch.autograd.Function):
                      tokens.shape[0] if has_tokens else 0, tok_offset, ignore_index, stats.data_ptr(),
                      _lib.ptr(g_lp), _lib.ptr(g_h), _lib.ptr(g_kl), grad.data_ptr(), K * V, V, _lib.stream_of(dev))
         return grad, None, None, None, None
+
+
+def _window_index(episode_offsets, seq_len: int, *, stride: int = 1, pad: str = "edge"):
+    """The window table of a dataset of episodes: CPU int64 ``(starts, ends, episode)``, one entry per
+    training sample, for ``encode_windows``.
+
+    ``episode_offsets`` [E + 1], non-decreasing (a host sequence or CPU tensor): episode ``e`` is
+    frames ``off[e] .. off[e + 1] - 1`` of the flat buffer.  ``pad="edge"``: every start
+    ``off[e] + k * stride < off[e + 1]`` is a window (ceil(L / stride) per episode of length L), and
+    a window that reaches past the episode repeats its last frame -- LeRobot's padding rule.
+    ``pad="valid"``: only starts with ``start + seq_len <= off[e + 1]`` ((L - seq_len) // stride + 1
+    per episode, none if L < seq_len).  ``ends`` is the window's episode end ``off[e + 1]``.
+    Vectorised: no loop over windows, no GPU."""
+    off = torch.as_tensor(episode_offsets)
+    if off.device.type != "cpu" or off.dim() != 1 or off.numel() < 1 or off.dtype.is_floating_point:
+        raise ValueError("episode_offsets must be a host sequence of E + 1 integer frame offsets")
+    off = off.to(torch.int64)
+    if stride < 1 or seq_len < 1:
+        raise ValueError(f"stride={stride} and seq_len={seq_len} must be >= 1")
+    if pad not in ("edge", "valid"):
+        raise ValueError(f"pad={pad!r} is not 'edge' or 'valid'")
+    length = off[1:] - off[:-1]
+    if bool((length < 0).any()) or int(off[0]) < 0:
+        raise ValueError("episode_offsets must be non-negative and non-decreasing")
+    if pad == "edge":
+        n = (length + (stride - 1)) // stride
+    else:
+        n = torch.where(length >= seq_len, (length - seq_len) // stride + 1, torch.zeros_like(length))
+    episode = torch.repeat_interleave(torch.arange(n.numel(), dtype=torch.int64), n)
+    first = torch.cumsum(n, 0) - n                       # index of each episode's first window
+    k = torch.arange(episode.numel(), dtype=torch.int64) - first[episode]
+    starts = off[:-1][episode] + k * stride
+    ends = off[1:][episode]
+    return starts, ends, episode
 
 
 class BEASTBsplineTokenizer(TokenizerBase):
@@ -1085,6 +1120,156 @@ class BEASTBsplineTokenizer(TokenizerBase):
             self.update_weights_bounds_per_batch(params, process_group=process_group)
         tokens = self._quantize(params, 0, dev, mode=1)
         return tokens, {"params": params, **self._cond_dict()}
+
+    # ===============================================
+    #     - encoding windows of an episode buffer -
+    # ===============================================
+
+    def window_index(self, episode_offsets, *, stride=1, pad="edge"):
+        """The window table of a dataset of episodes for ``encode_windows``: CPU int64
+        ``(starts, ends, episode)``, one entry per training sample of ``seq_len`` steps
+        (``pad="edge"``: every start inside an episode, the last frame repeated past its end;
+        ``pad="valid"``: whole windows only).  Vectorised, no GPU."""
+        return _window_index(episode_offsets, int(self.times.numel()), stride=stride, pad=pad)
+
+    def _fit_windows(self, frames, starts, ends, tokens_offset: Optional[int], want_counts: bool = False):
+        """One launch of beast_encode_windows_f32 (csrc/windows.hip).  Returns (params, tokens or
+        None, valid, tile counts or None, device).  The argument checks run before the device is
+        asked for."""
+        if self._basis.conditioned:
+            raise NotImplementedError(
+                "encode_windows supports init_cond_order = end_cond_order = 0 only: the conditions are kept "
+                "per batch from y0, y1 of materialised trajectories (uni_bspline.py:499-550), and a window "
+                "table has none")
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.as_tensor(frames)
+        if frames.dim() != 2:
+            raise ValueError(f"frames must be [R, num_dof] (a flat frame buffer); got {tuple(frames.shape)}")
+        R, Din = frames.shape
+        min_din = max(self.joint_indices + self.gripper_indices, default=-1) + 1
+        if Din < min_din:
+            raise IndexError(f"index {min_din - 1} is out of bounds for dimension 1 with size {Din}")
+        if not isinstance(starts, torch.Tensor):
+            starts = torch.as_tensor(starts)
+        if not isinstance(ends, torch.Tensor):
+            ends = torch.as_tensor(ends)
+        if (starts.dim() != 1 or starts.shape != ends.shape or starts.dtype is not torch.int64
+                or ends.dtype is not torch.int64):
+            raise ValueError(f"starts / ends must be int64 [W] tables of one length; got {tuple(starts.shape)} "
+                             f"{starts.dtype} and {tuple(ends.shape)} {ends.dtype}")
+        W = starts.shape[0]
+        # host tables are checked here; a device table is not synchronised on (the kernel clamps it)
+        if W and starts.device.type == "cpu" and ends.device.type == "cpu":
+            if bool(((starts < 0) | (starts >= ends) | (ends > R)).any()):
+                raise ValueError(f"window table out of range: need 0 <= start < end <= R={R} for every window")
+        p = self._plan()
+        dev, T = p.dev, p.T
+        # the hot path (device-resident fp32 frames and tables) pays for no torch call it does not need
+        if frames.device != dev or frames.dtype is not torch.float32:
+            frames = frames.to(dev, dtype=torch.float32)
+        st = frames.stride()
+        if R and (st[1] != 1 or (R > 1 and st[0] < Din)):
+            frames = frames.contiguous()
+            st = frames.stride()
+        if starts.device != dev:
+            starts = starts.to(dev)
+        if ends.device != dev:
+            ends = ends.to(dev)
+        if W > 1 and starts.stride(0) != 1:
+            starts = starts.contiguous()
+        if W > 1 and ends.stride(0) != 1:
+            ends = ends.contiguous()
+        DN = self.num_dof * self.num_basis
+        params = torch.empty((W, DN), dtype=torch.float32, device=dev)
+        tokens = p_tok = p_wmn = p_wmx = None
+        if tokens_offset is not None:
+            tokens = torch.empty((W, DN), dtype=torch.int64, device=dev)
+            p_tok, p_wmn, p_wmx = tokens.data_ptr(), p.p_wmn, p.p_wmx
+        # min(T, end - start): the subtraction lands in int32 (two launches in all)
+        valid = torch.empty((W,), dtype=torch.int32, device=dev)
+        torch.sub(ends, starts, out=valid).clamp_(max=T)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev) if want_counts else None
+        if W:   # an empty tensor has no address to pass
+            rc = p.enc_win(frames.data_ptr(), R, st[0], st[1], Din, starts.data_ptr(), ends.data_ptr(), W, T,
+                           self.num_dof, self.joint_dof, p.p_src, p.p_proj, self.num_basis, p_wmn, p_wmx,
+                           self.vocab_size, tokens_offset or 0, params.data_ptr(), p_tok,
+                           None if counts is None else counts.data_ptr(), _lib.raw_stream(p.idx))
+            if rc:
+                _lib.check(rc, "beast_encode_windows_f32")
+        return params, tokens, valid, counts, dev
+
+    @torch.no_grad()
+    def encode_windows(self, frames, starts, ends, update_bounds=False, *, respect_llm_vocab_size=True,
+                       process_group=None, return_tile_counts=False):
+        """``encode`` of the windows of a flat frame buffer, without materialising them: (tokens int64
+        [W, num_basis*num_dof], {"params": fp32 [W, num_dof*num_basis], "valid": int32 [W], ...}) from
+        one launch of ``beast_encode_windows_f32``.
+
+        ``frames`` [R, >= num_dof], any row stride: every episode's frames, one after another.
+        ``starts`` / ``ends`` int64 [W], on the host or the device (:meth:`window_index` builds them
+        from episode offsets): window ``w`` is the trajectory ``frames[min(starts[w] + t, ends[w] - 1)]``
+        for ``t < seq_len`` -- the next ``seq_len`` actions, the episode's last frame repeated past its
+        end (LeRobot's padding rule).  Tokens and params are bitwise those of ``encode`` on the gathered
+        [W, seq_len, D] tensor; ``valid`` is ``min(seq_len, end - start)``, the samples that are no
+        padding.  Host tables are range-checked (``ValueError``); device tables are not read back:
+        the kernel clamps them into the buffer, so a bad one gives wrong numbers, never a fault
+        -- and ``valid`` is then ``min(seq_len, end - start)`` of the table AS GIVEN (it may be
+        negative, or differ from the rows the kernel used after its clamp).
+
+        ``update_bounds`` / ``process_group`` / ``respect_llm_vocab_size`` as in ``encode``.
+        ``return_tile_counts`` adds ``"tile_counts"``: int32 [2], the kernel's tiles that shared one
+        staged segment / that were gathered window by window.  Tokenizers with init / end conditions
+        raise ``NotImplementedError``."""
+        offset = self._offset(respect_llm_vocab_size)
+        if update_bounds:
+            params, _, valid, counts, dev = self._fit_windows(frames, starts, ends, None, return_tile_counts)
+            self.update_weights_bounds_per_batch(params, process_group=process_group)
+            tokens = self._quantize(params, offset, dev, mode=0)
+        else:
+            params, tokens, valid, counts, _ = self._fit_windows(frames, starts, ends, offset, return_tile_counts)
+        info = {"params": params, "valid": valid, **self._cond_dict()}
+        if return_tile_counts:
+            info["tile_counts"] = counts
+        return tokens, info
+
+    @torch.no_grad()
+    def encode_continuous_windows(self, frames, starts, ends, update_bounds=False, *, process_group=None):
+        """``encode_continuous`` of the windows of a frame buffer: the params of ``encode_windows``
+        normalised to [-1, 1] in (t d) order."""
+        params, _, valid, _, dev = self._fit_windows(frames, starts, ends, None)
+        if update_bounds:
+            self.update_weights_bounds_per_batch(params, process_group=process_group)
+        tokens = self._quantize(params, 0, dev, mode=1)
+        return tokens, {"params": params, "valid": valid, **self._cond_dict()}
+
+    @torch.no_grad()
+    def fit_parameters_windows(self, frames, starts, ends, *, chunk_windows=1 << 20, process_group=None):
+        """``fit_parameters`` over the windows of a frame buffer: w_min / w_max become the 1 % / 99 %
+        quantiles of every window's fitted params.  The table is fitted ``chunk_windows`` windows at
+        a time and the quantile kernels read the chunks' params in place.  With ``process_group``
+        every rank fits its own table and the quantiles are those of the union."""
+        from .quantile import column_quantiles
+        from .bpe_train import no_reduce, torch_dist_reducer
+
+        if chunk_windows < 1:
+            raise ValueError("chunk_windows must be >= 1")
+        starts, ends = torch.as_tensor(starts), torch.as_tensor(ends)
+        if starts.dim() != 1 or ends.dim() != 1:
+            self._fit_windows(frames, starts, ends, None)   # raises: the tables' shape
+        W = starts.shape[0]
+        params = []
+        for i in range(0, max(W, 1), chunk_windows):
+            pr = self._fit_windows(frames, starts[i:i + chunk_windows], ends[i:i + chunk_windows], None)[0]
+            if pr.shape[0]:
+                params.append(pr)
+        if not params and process_group is None:
+            raise RuntimeError("No parameters were gathered: the window table is empty.")
+        allp = params if params else torch.empty((0, self.num_dof * self.num_basis), device=self._dev())
+        reduce = no_reduce if process_group is None else torch_dist_reducer(
+            None if process_group is True else process_group)
+        q = column_quantiles(allp, [0.01, 0.99], reduce)
+        self.w_min.copy_(q[0].to(self.w_min.device))
+        self.w_max.copy_(q[1].to(self.w_max.device))
 
     # ===============================================
     #           - tokenizer LLM tokenization -

@@ -1,7 +1,8 @@
 // Encode kernels (codec.hip's second layer): k_encode, the 4- / 7-wave tile walk for every shape,
 // and k_encode_v, one wave per trajectory for the fixed BEAST shapes; their argument blocks and
 // LDS layouts.  Tokens and params of the two are bit-identical (shared quantiser, same products
-// in the same order).
+// in the same order).  A tile's fit and epilogue are enc_fit_tile / enc_store_tile, which
+// windows.hip's k_encode_windows runs over its own image of the same layout.
 #pragma once
 
 #include "codec_device.h"
@@ -66,16 +67,156 @@ __host__ __device__ inline EncSmem enc_smem(int T, int Tp, int Dl, int D, int N,
   return s;
 }
 
+// The fit of one tile, shared by every kernel that walks tiles (k_encode, windows.hip's
+// k_encode_windows): params[j][d][n] = sum_t P_kind[n][t] y[j][t][d]  (f32 MFMA 16x16x4; A = P,
+// B = y) into the (d n) image pb.  A wave owns two column tiles per pass (two independent chains),
+// operands pointer-stepped through LDS; rows t >= T (tail step) meet a zero A column.
+// rows_of(j, base, last): trajectory j's sample t is row min(t, last) of the image, rows of Dl
+// floats from float `base` of Y (last <= T - 1; a window that ends early repeats its last row);
+// col_of(d): the column of DoF d inside a row.
+template <int TBT, class S, class RowsOf, class ColOf>
+__device__ __forceinline__ void enc_fit_tile(const Geom& g, const Dims<S>& m, const float* P, const float* Y, float* pb,
+                                             int Dl, int nb, int wave, int lr, int lk, bool first, RowsOf rows_of,
+                                             ColOf col_of) {
+  constexpr int NW = S::W;
+  const int D = m.D, N = m.N, T = m.T, Tp = m.Tp, DN = D * N;
+  const int nq = n_coltiles<TBT>(m);
+  for (int q0 = wave; q0 < nq; q0 += NW * 2) {
+    int j0, d0, k0, j1, d1, k1;
+    bool ok0, ok1;
+    tile_col<TBT>(g, m, q0, lr, j0, d0, k0, ok0);
+    tile_col<TBT>(g, m, min(q0 + NW, nq - 1), lr, j1, d1, k1, ok1);
+    ok0 = ok0 && j0 < nb;
+    ok1 = ok1 && j1 < nb && (q0 + NW < nq);
+    const int c0 = col_of(d0);
+    const int c1 = col_of(d1);
+    int base0, last0, base1, last1;
+    rows_of(j0, base0, last0);
+    rows_of(j1, base1, last1);
+    // K-steps in chunks of ECH: every LDS operand of a chunk is read before its MFMAs and
+    // the next chunk's reads are issued before them too (one LDS round trip per chunk);
+    // even / odd steps accumulate separately (two chains per tile).  Step s covers rows
+    // t = 4s + lane/16, clamped to the trajectory's last row (the zero-padded P columns meet
+    // the rows t >= T).
+    const int nst = (T + 3) >> 2;
+    const bool two = q0 + NW < nq;   // wave-uniform: a second column tile this pass
+    const float* pa0 = P + (k0 * 16 + lr) * Tp + lk;
+    const float* pa1 = P + (k1 * 16 + lr) * Tp + lk;
+    const float* yc0 = Y + base0 + c0;
+    const float* yc1 = Y + base1 + c1;
+    float4_t acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
+    float xa[ECH], ya[ECH], xb[ECH], yb[ECH];
+#pragma unroll
+    for (int i = 0; i < ECH; ++i) {
+      const int t = 4 * i + lk;
+      xa[i] = pa0[4 * i]; ya[i] = yc0[min(t, last0) * Dl]; xb[i] = pa1[4 * i]; yb[i] = yc1[min(t, last1) * Dl];
+    }
+    for (int c = 0; c < nst; c += ECH) {
+      float nxa[ECH], nya[ECH], nxb[ECH], nyb[ECH];
+#pragma unroll
+      for (int i = 0; i < ECH; ++i) {   // next chunk (reads past the end land in LDS slack, unused)
+        const int st = c + ECH + i, t = 4 * st + lk;
+        nxa[i] = pa0[4 * st]; nya[i] = yc0[min(t, last0) * Dl]; nxb[i] = pa1[4 * st]; nyb[i] = yc1[min(t, last1) * Dl];
+      }
+#pragma unroll
+      for (int i = 0; i < ECH; ++i) {
+        if (c + i < nst) {   // wave-uniform
+          if (i & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[i], ya[i], acc1, 0, 0, 0);
+          else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[i], ya[i], acc0, 0, 0, 0);
+          if (two) {
+            if (i & 1) acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[i], yb[i], acc3, 0, 0, 0);
+            else acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[i], yb[i], acc2, 0, 0, 0);
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < ECH; ++i) { xa[i] = nxa[i]; ya[i] = nya[i]; xb[i] = nxb[i]; yb[i] = nyb[i]; }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      acc0[r] = __fadd_rn(acc0[r], acc1[r]);
+      acc2[r] = __fadd_rn(acc2[r], acc3[r]);
+    }
+    // f32 C/D map: col = lane & 15, row = (lane >> 4) * 4 + r.  Each lane writes its params
+    // into the (d n) image; quantisation happens in the epilogue, spread over every thread.
+    if (first && q0 == wave) STAMP(0, 8);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = lk * 4 + r;
+      if (n < N) {
+        if (ok0) pb[j0 * DN + d0 * N + n] = acc0[r];
+        if (ok1) pb[j1 * DN + d1 * N + n] = acc2[r];
+      }
+    }
+  }
+}
+
+// The epilogue of one tile (rows b0 .. b0 + nb of the outputs): params (d n) out of the image pb,
+// tokens (n d) quantised from it with the bounds kq / wlo / whi, both contiguous per tile.
+template <class S>
+__device__ __forceinline__ void enc_store_tile(const EncArgs& a, const Dims<S>& m, const float* pb, const float4* kq,
+                                               const float* wlo, const float* whi, int64_t b0, int nb, float vm1,
+                                               bool first) {
+  constexpr int NT = S::W * 64;
+  const Geom& g = a.g;
+  const int D = m.D, N = m.N, per = m.per, DN = D * N;
+  const int tid = threadIdx.x;
+  const bool quant = a.tokens_out != nullptr;
+  constexpr int SP = (S::W == 7) ? LAT_SP : 0;   // the 7-wave shape is the latency regime's
+  if (a.params_out != nullptr && (a.phases & 4)) store_out<NT, SP>(a.params_out + b0 * DN, pb, nb * DN);
+  if (first) STAMP(0, 5);
+  if (quant && (a.phases & 8)) {
+    // tokens in (n d) order: each thread quantises 4 consecutive tokens from the (d n)
+    // params image (fast bins; the exactly-rounded chain only where one lies near a
+    // rounding boundary), widens them to int64 + offset and stores 2 x 16 B.
+    const int total = nb * per;
+    long long* tout = a.tokens_out + b0 * per;
+    const unsigned long long off = (unsigned long long)a.tok_offset;
+    auto col_of = [&](int e, int& pj) {   // token e of the tile -> (d n) column, trajectory
+      const int j = (int)div_by<S>((uint32_t)e, per, g.fd_per);
+      const int r = e - j * per;
+      const int n = (int)div_by<S>((uint32_t)r, D, g.fd_D);
+      pj = j * DN;
+      return (r - n * D) * N + n;
+    };
+    int done = 0;
+    if ((((uintptr_t)tout) & 15) == 0) {
+      const int n4 = total >> 2;
+      for (int i = tid; i < n4; i += NT) {
+        int bin[4], c[4], pj[4];
+        float pv[4], lo[4], hi[4], k[4];
+        // every LDS operand of the 4 tokens is requested before any is used (one round trip)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) c[u] = col_of(4 * i + u, pj[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          pv[u] = pb[pj[u] + c[u]];
+          const float4 q = kq[c[u]];
+          lo[u] = q.x; hi[u] = q.y; k[u] = q.z;
+        }
+        beast::quantize_bins(pv, lo, hi, vm1, bin, k);
+        st16<SP>(tout + 4 * i, beast::widen_bin(bin[0], off), beast::widen_bin(bin[1], off));
+        st16<SP>(tout + 4 * i + 2, beast::widen_bin(bin[2], off), beast::widen_bin(bin[3], off));
+      }
+      done = n4 << 2;
+    }
+    for (int e = done + tid; e < total; e += NT) {
+      int pj;
+      const int c = col_of(e, pj);
+      tout[e] = beast::widen_bin(beast::quantize_bin(pb[pj + c], wlo[c], whi[c], vm1), off);
+    }
+  }
+}
+
 template <int TBT, bool FAST, class S>
 __global__ __launch_bounds__(S::W * 64) void k_encode(EncArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NW = S::W, NT = NW * 64;
   const Geom& g = a.g;
   const Dims<S> m(g);
-  const int D = m.D, N = m.N, T = m.T, Tp = m.Tp, per = m.per, DN = D * N;
+  const int D = m.D, N = m.N, T = m.T, Tp = m.Tp, DN = D * N;
   const int Dl = FAST ? (S::DL ? S::DL : a.row_elems) : D;
   const int nkinds = (m.nj < D) ? 2 : 1;
-  const int nq = n_coltiles<TBT>(m);
   const EncSmem L = enc_smem<TBT>(T, Tp, Dl, D, N, nkinds);
   float* P = reinterpret_cast<float*>(smem + L.P);
   float* Y = reinterpret_cast<float*>(smem + L.Y);
@@ -136,123 +277,19 @@ __global__ __launch_bounds__(S::W * 64) void k_encode(EncArgs a) {
       for (int i = tid; i < DN; i += NT)
         kq[i] = make_float4(wlo[i], whi[i], beast::quantize_scale(wlo[i], whi[i], vm1), 0.0f);
 
-    // ---- fit: params[j][d][n] = sum_t P_kind[n][t] y[j][t][d]  (f32 MFMA 16x16x4; A = P, B = y).
-    //      A wave owns two column tiles per pass (two independent chains), operands
-    //      pointer-stepped through LDS; rows t >= T (tail step) meet a zero A column.
-    for (int q0 = wave; (a.phases & 2) && q0 < nq; q0 += NW * 2) {
-      int j0, d0, k0, j1, d1, k1;
-      bool ok0, ok1;
-      tile_col<TBT>(g, m, q0, lr, j0, d0, k0, ok0);
-      tile_col<TBT>(g, m, min(q0 + NW, nq - 1), lr, j1, d1, k1, ok1);
-      ok0 = ok0 && j0 < nb;
-      ok1 = ok1 && j1 < nb && (q0 + NW < nq);
-      const int c0 = FAST ? min(max(lcol[d0], 0), Dl - 1) : d0;
-      const int c1 = FAST ? min(max(lcol[d1], 0), Dl - 1) : d1;
-      // K-steps in chunks of ECH: every LDS operand of a chunk is read before its MFMAs and
-      // the next chunk's reads are issued before them too (one LDS round trip per chunk);
-      // even / odd steps accumulate separately (two chains per tile).  Step s covers rows
-      // t = 4s + lane/16, clamped to T - 1 (the zero-padded P columns meet them).
-      const int nst = (T + 3) >> 2;
-      const bool two = q0 + NW < nq;   // wave-uniform: a second column tile this pass
-      const float* pa0 = P + (k0 * 16 + lr) * Tp + lk;
-      const float* pa1 = P + (k1 * 16 + lr) * Tp + lk;
-      const float* yc0 = Y + j0 * T * Dl + c0;
-      const float* yc1 = Y + j1 * T * Dl + c1;
-      float4_t acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
-      float xa[ECH], ya[ECH], xb[ECH], yb[ECH];
-#pragma unroll
-      for (int i = 0; i < ECH; ++i) {
-        const int row = min(4 * i + lk, T - 1) * Dl;
-        xa[i] = pa0[4 * i]; ya[i] = yc0[row]; xb[i] = pa1[4 * i]; yb[i] = yc1[row];
-      }
-      for (int c = 0; c < nst; c += ECH) {
-        float nxa[ECH], nya[ECH], nxb[ECH], nyb[ECH];
-#pragma unroll
-        for (int i = 0; i < ECH; ++i) {   // next chunk (reads past the end land in LDS slack, unused)
-          const int st = c + ECH + i, row = min(4 * st + lk, T - 1) * Dl;
-          nxa[i] = pa0[4 * st]; nya[i] = yc0[row]; nxb[i] = pa1[4 * st]; nyb[i] = yc1[row];
-        }
-#pragma unroll
-        for (int i = 0; i < ECH; ++i) {
-          if (c + i < nst) {   // wave-uniform
-            if (i & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[i], ya[i], acc1, 0, 0, 0);
-            else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[i], ya[i], acc0, 0, 0, 0);
-            if (two) {
-              if (i & 1) acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[i], yb[i], acc3, 0, 0, 0);
-              else acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[i], yb[i], acc2, 0, 0, 0);
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < ECH; ++i) { xa[i] = nxa[i]; ya[i] = nya[i]; xb[i] = nxb[i]; yb[i] = nyb[i]; }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc0[r] = __fadd_rn(acc0[r], acc1[r]);
-        acc2[r] = __fadd_rn(acc2[r], acc3[r]);
-      }
-      // f32 C/D map: col = lane & 15, row = (lane >> 4) * 4 + r.  Each lane writes its params
-      // into the (d n) image; quantisation happens in the epilogue, spread over every thread.
-      if (tile == blockIdx.x && q0 == wave) STAMP(0, 8);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = lk * 4 + r;
-        if (n < N) {
-          if (ok0) pb[j0 * DN + d0 * N + n] = acc0[r];
-          if (ok1) pb[j1 * DN + d1 * N + n] = acc2[r];
-        }
-      }
-    }
+    // ---- fit: every trajectory's rows are its own T rows of the [j][t][Dl] image
+    if (a.phases & 2)
+      enc_fit_tile<TBT, S>(
+          g, m, P, Y, pb, Dl, nb, wave, lr, lk, tile == blockIdx.x,
+          [&](int j, int& base, int& last) { base = j * T * Dl; last = T - 1; },
+          [&](int d) { return FAST ? min(max(lcol[d], 0), Dl - 1) : d; });
     if (tile == blockIdx.x) STAMP(0, 3);
     if (tile == blockIdx.x + gridDim.x) STAMP(0, 13);
     __syncthreads();
     if (tile == blockIdx.x) STAMP(0, 4);
 
     // ---- epilogue: params (d n) and tokens (n d), both contiguous per tile
-    constexpr int SP = (S::W == 7) ? LAT_SP : 0;   // the 7-wave shape is the latency regime's
-    if (a.params_out != nullptr && (a.phases & 4)) store_out<NT, SP>(a.params_out + b0 * DN, pb, nb * DN);
-    if (tile == blockIdx.x) STAMP(0, 5);
-    if (quant && (a.phases & 8)) {
-      // tokens in (n d) order: each thread quantises 4 consecutive tokens from the (d n)
-      // params image (fast bins; the exactly-rounded chain only where one lies near a
-      // rounding boundary), widens them to int64 + offset and stores 2 x 16 B.
-      const int total = nb * per;
-      long long* tout = a.tokens_out + b0 * per;
-      const unsigned long long off = (unsigned long long)a.tok_offset;
-      auto col_of = [&](int e, int& pj) {   // token e of the tile -> (d n) column, trajectory
-        const int j = (int)div_by<S>((uint32_t)e, per, g.fd_per);
-        const int r = e - j * per;
-        const int n = (int)div_by<S>((uint32_t)r, D, g.fd_D);
-        pj = j * DN;
-        return (r - n * D) * N + n;
-      };
-      int done = 0;
-      if ((((uintptr_t)tout) & 15) == 0) {
-        const int n4 = total >> 2;
-        for (int i = tid; i < n4; i += NT) {
-          int bin[4], c[4], pj[4];
-          float pv[4], lo[4], hi[4], k[4];
-          // every LDS operand of the 4 tokens is requested before any is used (one round trip)
-#pragma unroll
-          for (int u = 0; u < 4; ++u) c[u] = col_of(4 * i + u, pj[u]);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            pv[u] = pb[pj[u] + c[u]];
-            const float4 q = kq[c[u]];
-            lo[u] = q.x; hi[u] = q.y; k[u] = q.z;
-          }
-          beast::quantize_bins(pv, lo, hi, vm1, bin, k);
-          st16<SP>(tout + 4 * i, beast::widen_bin(bin[0], off), beast::widen_bin(bin[1], off));
-          st16<SP>(tout + 4 * i + 2, beast::widen_bin(bin[2], off), beast::widen_bin(bin[3], off));
-        }
-        done = n4 << 2;
-      }
-      for (int e = done + tid; e < total; e += NT) {
-        int pj;
-        const int c = col_of(e, pj);
-        tout[e] = beast::widen_bin(beast::quantize_bin(pb[pj + c], wlo[c], whi[c], vm1), off);
-      }
-    }
+    enc_store_tile<S>(a, m, pb, kq, wlo, whi, b0, nb, vm1, tile == blockIdx.x);
     if (tile == blockIdx.x) STAMP(0, 6);
     if (tile == blockIdx.x + gridDim.x) STAMP(0, 14);
   }

@@ -41,8 +41,8 @@ extern "C" {
 #define BEAST_E_UNSUPPORTED (-3) /* shape outside the kernels' envelope       */
 #define BEAST_E_WORKSPACE (-4)   /* workspace too small                       */
 
-#define BEAST_ABI_VERSION 4   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
-                                 4: beast_score_rows, beast_score_rows_bwd */
+#define BEAST_ABI_VERSION 5   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
+                                 4: beast_score_rows, beast_score_rows_bwd; 5: beast_encode_windows_f32 */
 
 int beast_abi_version(void);
 const char* beast_last_error(void);
@@ -191,6 +191,38 @@ int beast_encode_rows_f32(const float* traj, int64_t B, int T, int64_t sb, int64
                           int n_knots_grip, int degree, int N, double reg, const float* w_min,
                           const float* w_max, int vocab, int64_t tok_offset, float* params_out,
                           int64_t* tokens_out, void* stream);
+
+/* beast_encode_f32 on WINDOWS of a flat frame buffer, one launch, without materialising them:
+ * what a dataset of episodes feeds the tokenizer (LeRobot's rule: the next T actions from a
+ * frame, the episode's last frame repeated past its end).
+ *   frames[r*sr + c*sd]   fp32 [R][row_elems], element strides; a row ends before the next
+ *                         begins (sr >= (row_elems-1)*sd + 1), so all of it lies below frames + R*sr
+ *   win_start, win_end    DEVICE int64 [W]: window w covers rows win_start[w] .. win_end[w] - 1 and
+ *                         its sample t (0 <= t < T) is row min(win_start[w] + t, win_end[w] - 1)
+ * followed by exactly beast_encode_f32 (projection, clamp, quantiser, (d n) -> (n d), offset):
+ * params_out [W][D*N] and tokens_out [W][N*D] are bitwise those of beast_encode_f32 on the gathered
+ * [W][T][row_elems] tensor.  proj, dof_src, w_min / w_max, vocab, tok_offset and the nullable
+ * outputs mean what they mean there; a dof_src entry outside [0, row_elems) is clamped into the
+ * row on either path below (as beast_encode_f32's contiguous path does).
+ * The tables are not trusted: the kernel clamps win_start into [0, R-1] and win_end into
+ * [win_start+1, R], so nothing outside frames[0 .. R*sr) is read whatever they hold (a bad table
+ * gives wrong numbers, never a fault).
+ * One workgroup takes a tile of consecutive windows.  Where the rows the tile's windows cover
+ * (min start .. max min(start+T, end)) number at most tile * T and sd == 1, they are staged in LDS
+ * once and shared by the windows (a dense stride-1 table reads every frame about once, not T
+ * times); otherwise the tile's windows are gathered one by one.  Same result either way.
+ *   tile_counts  nullable uint32[2], zeroed by the caller: += 1 per tile to [0] (shared segment)
+ *                or [1] (gathered); for tests and tools.
+ * BEAST_E_INVALID: a null required pointer, both outputs null, R < 1 with W > 0, W < 0, T < 1,
+ * N < 1, D < 1, row_elems < 1, n_joint outside [0, D], a negative stride, overlapping rows,
+ * tokens_out with vocab < 2 or without bounds.  BEAST_E_UNSUPPORTED outside beast_encode_f32's
+ * envelope: N <= 16, T <= 256, D <= 64.  W == 0 is a no-op.  The stream parameter is the header's
+ * `stream` in every respect. */
+int beast_encode_windows_f32(const float* frames, int64_t R, int64_t sr, int64_t sd, int row_elems,
+                             const int64_t* win_start, const int64_t* win_end, int64_t W, int T,
+                             int D, int n_joint, const int32_t* dof_src, const float* proj, int N,
+                             const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
+                             float* params_out, int64_t* tokens_out, uint32_t* tile_counts, void* windows_stream);
 
 /* ------------------------------------------------------------- H6 - H8 ---
  * Replaces BEASTBsplineTokenizer.decode + reconstruct_traj (beast/
