@@ -29,6 +29,7 @@ OPT_BPE_ENCODE_MODE = 5
 OPT_BPE_DEDUP_KEY_BITS = 6
 OPT_BPE_TRAIN_HOST_LOOP = 7
 OPT_LAST_CODEC_LAUNCH = 8   # read-only
+OPT_LAST_LAUNCH_GRID = 9    # read-only
 # beast_bpe_loop_batch flags, and the int32 words of the loop state a host reads
 BPE_BATCH_INIT = 1
 BPE_BATCH_NO_MERGE = 2
@@ -236,6 +237,11 @@ def decode_codec_launch(v: int) -> CodecLaunch:
 def last_codec_launch() -> CodecLaunch:
     """The kernel choice of this process's last encode / reconstruct launch (tests, tools)."""
     return decode_codec_launch(load().beast_get_option(OPT_LAST_CODEC_LAUNCH))
+
+
+def last_launch_grid() -> int:
+    """gridDim.x of this process's last kernel launch through the library, 0 before any (tests)."""
+    return load().beast_get_option(OPT_LAST_LAUNCH_GRID)
 
 
 def ptr(t: Optional[torch.Tensor]):

@@ -445,6 +445,7 @@ extern "C" int beast_set_option(int option, int value) {
     return BEAST_OK;
   }
   BEAST_REQUIRE(option != BEAST_OPT_LAST_CODEC_LAUNCH, "BEAST_OPT_LAST_CODEC_LAUNCH is read-only");
+  BEAST_REQUIRE(option != BEAST_OPT_LAST_LAUNCH_GRID, "BEAST_OPT_LAST_LAUNCH_GRID is read-only");
   BEAST_REQUIRE(false, "unknown option %d", option);
   return BEAST_E_INVALID;
 }
@@ -457,6 +458,7 @@ extern "C" int beast_get_option(int option) {
   if (option == BEAST_OPT_BPE_DEDUP_KEY_BITS) return beast::g_bpe_dedup_key_bits;
   if (option == BEAST_OPT_BPE_TRAIN_HOST_LOOP) return beast::g_bpe_train_host;
   if (option == BEAST_OPT_LAST_CODEC_LAUNCH) return g_last_launch.load(std::memory_order_relaxed);
+  if (option == BEAST_OPT_LAST_LAUNCH_GRID) return (int)beast::g_last_launch_grid.load(std::memory_order_relaxed);
   beast::set_error("unknown option %d", option);
   return BEAST_E_INVALID;
 }

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +23,8 @@ extern int g_bpe_dedup_key_bits;
 // BEAST_OPT_BPE_TRAIN_HOST_LOOP: beast_bpe_train's loop (tests: 1 host-driven, 2 rerun as after a
 // string-hash collision of the batched loop)
 extern int g_bpe_train_host;
+// BEAST_OPT_LAST_LAUNCH_GRID: gridDim.x of the last kernel launch.h started (read-only; 0 before any)
+extern std::atomic<unsigned> g_last_launch_grid;
 int hip_fail(hipError_t e, const char* what);
 // comm.hip: a rank's status agreed over the communicator (every rank must call it at the same
 // point).  Returns rc when it failed locally, the failing rank's code (message: which rank) when

@@ -142,6 +142,7 @@ int launch_typed(void (*kernel)(P...), FnCache& cache, dim3 grid, unsigned block
   hipFunction_t f;
   BEAST_TRY(function_of(reinterpret_cast<const void*>(kernel), cache, lds, q, what, f));
   void* params[] = {static_cast<void*>(&args)...};
+  beast::g_last_launch_grid.store(grid.x, std::memory_order_relaxed);   // BEAST_OPT_LAST_LAUNCH_GRID
   BEAST_HIP(hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, block, 1, 1, lds, q.s, params, nullptr), what);
   return BEAST_OK;
 }

@@ -75,6 +75,9 @@ const char* beast_last_error(void);
  *   bit 18      reconstruct basis operands in registers (0: in LDS, or read per row from memory)
  *   bit 19      output staged through LDS (0 only for k_reconstruct_rows' direct stores)
  *   bit 20      latency variant (write-through stores, one tile per CU) rather than the bulk one
+ * BEAST_OPT_LAST_LAUNCH_GRID (tests; read-only): gridDim.x of the last kernel this process launched
+ * through the library, whichever entry point started it; 0 before any launch.  A test reads it
+ * right after a call to prove that the persistent kernel it means to check walked several tiles.
  * Options are process-wide and not synchronised: set them before launching, not concurrently. */
 #define BEAST_OPT_GENERIC_KERNELS 1
 #define BEAST_OPT_BLOCK_WAVES 2
@@ -83,6 +86,7 @@ const char* beast_last_error(void);
 #define BEAST_OPT_BPE_DEDUP_KEY_BITS 6
 #define BEAST_OPT_BPE_TRAIN_HOST_LOOP 7
 #define BEAST_OPT_LAST_CODEC_LAUNCH 8
+#define BEAST_OPT_LAST_LAUNCH_GRID 9
 int beast_set_option(int option, int value);
 /* the option's current value (BEAST_E_INVALID for an unknown option) */
 int beast_get_option(int option);

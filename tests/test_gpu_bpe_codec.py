@@ -125,6 +125,11 @@ def test_codec_matches_live_hf(span, rows, width, vocab, encode_mode, gpu_device
     assert got_n == [w[:width] for w in want_g]
     if span == 255 and vocab == 6000:
         assert model.n_merges > 2048     # merge map too large for LDS: probed in HBM
+        # the same rows without the span bound are budgeted 4 byte symbols per code point, 560 a row:
+        # beyond the narrow per-row kernel's 384, so the per-row modes take its wide form with the
+        # map in HBM -- the one pairing of the two that no other case reaches
+        got_wide, status_wide = encode_rows(model, list(test), gpu_device)
+        assert not status_wide.any() and got_wide == want
 
 
 def test_bpe_tokenizer_api_and_errors(gpu_device):

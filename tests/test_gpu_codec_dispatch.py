@@ -210,6 +210,7 @@ ENCODE_ROWS = [
     # strided [B, 200, 24] takes the largest tile whose LDS layout fits
     ("limit_256x64", dict(T=256, D=64, N=16, B=9), "contig", "api", _dyn(1, False)),
     ("limit_200x24_cols", dict(T=200, D=24, N=16, B=9), "col_slice", "api", _dyn(4, False)),
+    ("limit_256x48_cols", dict(T=256, D=48, N=16, B=9), "col_slice", "api", _dyn(2, False)),
     # nullable outputs
     ("tokens_only_v", dict(K2, B=37), "contig", "tokens", V_LAT),
     ("params_only_v", dict(K2, B=37), "contig", "params", V_LAT),

@@ -76,11 +76,11 @@ def cu_count():
 
 # ------------------------------------------------------------------ raw entry point --
 @pytest.mark.parametrize("D", [1, 14, 64])
-@pytest.mark.parametrize("N", [1, 3, 10, 16])
+@pytest.mark.parametrize("N", [1, 3, 5, 8, 10, 16])
 def test_tile_and_vector_edges(N, D, gpu_device):
     """B around the tiles of 4 (and 16: tiles are capped at 256 / D trajectories), T_out 1, 7, 50
     (rows of 7 x D floats take the element loads where that is no multiple of four), every padding
-    of N; the layouts cycle over no grippers / two / all, extra permuted output columns, per-row
+    of N (N = 5 and 8 are the ends of KS = 2); the layouts cycle over no grippers / two / all, extra permuted output columns, per-row
     slabs, misaligned gradients and the order subsets, so each appears at several (B, T)."""
     layouts = itertools.cycle([dict(), dict(ndo=D + 5), dict(per_row=True), dict(misalign=True),
                                dict(ndo=D + 2, per_row=True, misalign=True)])
@@ -112,10 +112,24 @@ def test_layouts(nj, kw, gpu_device):
     check(gpu_device, make_inputs(37, 50, 14, nj, 10, (0, 1, 2), **kw), misalign=misalign)
 
 
+@pytest.mark.parametrize("bulk", [False, True], ids=["small_tiles", "bulk_tiles"])
+@pytest.mark.parametrize("per_row", [False, True], ids=["lds_slabs", "slabs_in_memory"])
+@pytest.mark.parametrize("orders", [(1,), (0, 2), (0, 1, 2)], ids=["ns1", "ns2", "ns3"])
+@pytest.mark.parametrize("N", [3, 5, 8, 10, 16])
+def test_every_instantiation(N, orders, per_row, bulk, gpu_device):
+    """k_reconstruct_derivs_bwd<KS, NS, LB, PF>: KS = ceil(N / 4) (both ends of KS = 2), NS
+    gradients given, the slabs staged in LDS or read per row, and the small tiles (PF = 1) or, from
+    two tiles of 16 per CU on, the bulk ones with two trajectories in flight (PF = 2); the last
+    tile is partial in both.  Every product is launched here at the smallest payload."""
+    B = 2 * 16 * cu_count() + 5 if bulk else 7
+    check(gpu_device, make_inputs(B, 4, 2, 1, N, orders, ndo=3, per_row=per_row), init_p=True)
+
+
 def test_bulk_variant_and_slabs_in_memory(gpu_device):
-    """From two tiles of 16 per CU on, the resident workgroups stride over tiles of 16 (full and
-    a partial last one); T_out 4096 puts the shared slabs in memory and cuts the time axis into
-    many chunks."""
+    """From two tiles of 16 per CU on, the launch takes tiles of 16 (full and a partial last one)
+    with two trajectories in flight per thread; at 2 CUs + 1 tiles the resident workgroups get one
+    tile each unless fewer than three fit a CU (tests/test_gpu_second_pass.py makes them stride).
+    T_out 4096 puts the shared slabs in memory and cuts the time axis into many chunks."""
     B = 2 * 16 * cu_count() + 5
     check(gpu_device, make_inputs(B, 4, 2, 1, 3, (0, 1, 2)))
     check(gpu_device, make_inputs(B, 4, 2, 2, 3, (1,), per_row=True), misalign=True)

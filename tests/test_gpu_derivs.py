@@ -254,7 +254,9 @@ def test_large_shapes(gpu_device):
     """Shared slabs too large for LDS are read from memory (T_out 700 at N 16); the envelope's
     corner D 64, N 16 and a wide output row still fit one tile's LDS; from two tiles of 16
     trajectories per CU on (B 20,000 covers up to 625 CUs) the bulk tile runs, here with full
-    tiles, with a partial last one (20,011 = 1,250 * 16 + 11), and on per-row slabs."""
+    tiles, with a partial last one (20,011 = 1,250 * 16 + 11), and on per-row slabs.  At these
+    payloads eight workgroups fit a CU, so from 157 CUs on every workgroup gets one tile only:
+    the loop over tiles is tests/test_gpu_second_pass.py's."""
     raw_case(gpu_device, 20000, 5, 14, 12, 10, (0, 1, 2))
     raw_case(gpu_device, 20011, 3, 2, 2, 6, (1, 2), ndo=3)
     raw_case(gpu_device, 20011, 1, 2, 1, 16, (0, 1), per_row=True, init_p=True)
@@ -262,6 +264,17 @@ def test_large_shapes(gpu_device):
     raw_case(gpu_device, 18, 5, 64, 60, 16, (0, 2))
     raw_case(gpu_device, 2, 4, 3, 3, 5, (1,), ndo=4096)
     raw_case(gpu_device, 2, 4096, 2, 2, 3, (0, 1))
+
+
+@pytest.mark.parametrize("bulk", [False, True], ids=["tiles_of_4", "tiles_of_16"])
+@pytest.mark.parametrize("per_row", [False, True], ids=["lds_slabs", "slabs_in_memory"])
+@pytest.mark.parametrize("N", [3, 5, 8, 10, 16])
+def test_every_instantiation(N, per_row, bulk, gpu_device):
+    """k_reconstruct_derivs<KS, LB, TB>: KS = ceil(N / 4) (both ends of KS = 2), the slabs staged in
+    LDS or read per row, tiles of 4 or -- from two tiles of 16 per CU on -- of 16; a partial last
+    tile in both.  Every product is launched here at the smallest payload."""
+    cus = torch.cuda.get_device_properties(gpu_device).multi_processor_count
+    raw_case(gpu_device, 2 * 16 * cus + 5 if bulk else 7, 3, 2, 1, N, (0, 1, 2), ndo=3, per_row=per_row, init_p=True)
 
 
 # -------------------------------------------------------------------- equivalence --

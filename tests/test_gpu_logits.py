@@ -128,6 +128,17 @@ def test_forward_and_backward_against_the_oracle(dtype, V, BK, gpu_device):
         check_against_oracle(l, tau, f"{dtype} V{V} B{BK[0]} K{BK[1]}", gpu_device)
 
 
+@pytest.mark.parametrize("V", [1025, 2048])
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_three_and_four_chunks_of_the_16_bit_types(dtype, V, gpu_device):
+    """A 16-bit chunk is 512 logits, so the V list above reaches one chunk (up to 257), two (1000)
+    and the online form (4097) for fp16 / bf16, never the three- and four-chunk in-register
+    instantiation: V 1025 (one element in the third chunk) and 2048 (four full chunks)."""
+    l = randn4((3, 7, V), DTYPES[dtype], gpu_device, seed=V)
+    for tau in (0.25, 1.0, 3.0):
+        check_against_oracle(l, tau, f"{dtype} V{V} B3 K7", gpu_device)
+
+
 def test_grid_stride_over_four_times_the_resident_rows(gpu_device):
     """At least four times as many rows as either launch keeps resident (the library says how many):
     every workgroup walks several groups of rows.  A row's outputs do not depend on the batch, so

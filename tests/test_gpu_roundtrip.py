@@ -162,14 +162,22 @@ def test_bounds_clip_both_sides_on_every_column(gpu_device):
     assert np.array_equal(c[0], 2 * s["clip_low"]) and np.array_equal(c[1], 2 * s["clip_high"])
 
 
-@pytest.mark.parametrize("shape,B", [(K2, 20001), (K1, 40001)], ids=["k2_20001", "k1_40001"])
-def test_many_tiles(shape, B, gpu_device):
-    """More tiles than the capped grid has workgroups (8-trajectory tiles on at most 6 workgroups per
-    CU at the default shape, 16-trajectory tiles on 8 per CU at D = 7), so a workgroup walks several
-    tiles and flushes its clip counts once; one trajectory in the last tile."""
+@pytest.mark.parametrize("shape,B,tile", [(K2, 20001, 8), (K1, 40001, 16), (K3, 20001, 8)],
+                         ids=["k2_20001", "k1_40001", "k3_20001"])
+def test_many_tiles(shape, B, tile, gpu_device):
+    """More tiles than the capped grid has workgroups (8-trajectory tiles at the default shape,
+    16-trajectory tiles at D = 7; the launch layer's grid is at most 2 x 8 workgroups per CU), so a
+    workgroup walks several tiles and flushes its clip counts once; one trajectory in the last tile.
+    B is the least batch for that, never below the parameter (enough up to 78 CUs): 32 tiles per CU
+    and one trajectory, and the grid read back after the launch is at most half the tiles."""
     tok, x64 = _setup(gpu_device, **shape)
+    cus = torch.cuda.get_device_properties(gpu_device).multi_processor_count
+    B = max(B, tile * 32 * cus + 1)
     x = _batch(x64, B)
-    _check(tok, x, *_raw(tok, x.data_ptr(), B, x.stride(), x.shape[2]))
+    out = _raw(tok, x.data_ptr(), B, x.stride(), x.shape[2])
+    grid, ntiles = _lib.last_launch_grid(), -(-B // tile)
+    assert 0 < grid and 2 * grid <= ntiles, f"grid {grid} for {ntiles} tiles: no workgroup is shown to walk two"
+    _check(tok, x, *out)
 
 
 @pytest.mark.parametrize("shape,B,generic", [(SMALL, 19, 0), (K2, 19, 1), (LIMIT, 3, 0)],

@@ -42,8 +42,10 @@ def assert_parity(got, ref, what=""):
 
 
 # B, T, N, degree, D, grippers: T a multiple of 4 or not and the cap of 256; N = degree + 1, 10, 16;
-# degree 0, 1, 3, 4; D = 1, 7, 14 with two grippers, 17 (a second 16-column tile), 64; B = 1, 3, 67
-# (a ragged last workgroup of 4 waves), 1,025 (the grid-stride loop with two kinds: 2,050 waves)
+# every degree the dispatch has a k_fit_rows<K> for (0 .. 8), each at N = degree + 1 and N = 16 from
+# degree 2 on; D = 1, 7, 14 with two grippers, 17 (a second 16-column tile), 64; B = 1, 3, 67 (a
+# ragged last workgroup of 4 waves), 1,025 (two kinds: 2,050 items, one per wave -- a wave takes a
+# second item only above 32 items per CU, which tests/test_gpu_second_pass.py arranges)
 SHAPES = [
     (3, 2, 2, 1, 1, ()),
     (67, 7, 4, 3, 7, ()),
@@ -52,6 +54,11 @@ SHAPES = [
     (67, 50, 10, 0, 7, ()),
     (1, 50, 5, 4, 64, (3, 40)),
     (1025, 50, 16, 3, 1, ()),
+    (5, 11, 3, 2, 3, ()), (5, 50, 16, 2, 2, (1,)),
+    (5, 19, 6, 5, 3, ()), (5, 50, 16, 5, 2, (1,)),
+    (5, 23, 7, 6, 3, ()), (5, 50, 16, 6, 2, (1,)),
+    (5, 26, 8, 7, 3, ()), (5, 50, 16, 7, 2, (1,)),
+    (5, 29, 9, 8, 3, ()), (5, 50, 16, 8, 2, (1,)),
 ]
 
 

@@ -159,16 +159,15 @@ def test_both_paths_are_seen_and_agree(gpu_device):
 
 @pytest.mark.parametrize("shuffled", [False, True])
 def test_more_tiles_than_workgroups(gpu_device, shuffled):
-    """40,001 windows are 5,001 tiles.  The launch has at most 16 workgroups per compute unit (the
-    launch layer's grid: 2 x at most 8 resident ones), so with 5,001 > 16 CUs every workgroup of the
-    grid walks two tiles or more: it stages the next image over the last one, rewrites the window
-    table and re-uses the params image and the quantiser constants.  With 28-byte rows the staged
-    segment's phase inside 16 bytes changes from tile to tile too."""
+    """The launch has at most 16 workgroups per compute unit (the launch layer's grid: 2 x at most 8
+    resident ones), so 32 tiles per CU and one window (never fewer than 40,001 windows) make every
+    workgroup of the grid walk two tiles or more: it stages the next image over the last one,
+    rewrites the window table and re-uses the params image and the quantiser constants.  The grid
+    read back after each launch is at most half the tiles.  With 28-byte rows the staged segment's
+    phase inside 16 bytes changes from tile to tile too."""
     tok, cols, T = make_tok(gpu_device, "d7")
-    R = 40001
+    R = max(40001, 8 * 32 * torch.cuda.get_device_properties(gpu_device).multi_processor_count + 1)
     ntiles = -(-R // 8)
-    assert torch.cuda.get_device_properties(gpu_device).multi_processor_count * 16 < ntiles, \
-        "the table is too small for this device: no workgroup would walk a second tile"
     frames = random_frames(R, cols, 41)
     s, e, _ = tok.window_index([0, 7000, R])
     if shuffled:
@@ -179,6 +178,8 @@ def test_more_tiles_than_workgroups(gpu_device, shuffled):
     fd = torch.from_numpy(frames).to(gpu_device)
     for _ in range(3):                                  # cold and warm caches
         got = tok.encode_windows(fd, s, e, return_tile_counts=True)
+        grid = _lib.last_launch_grid()
+        assert 0 < grid and 2 * grid <= ntiles, f"grid {grid} for {ntiles} tiles: no second tile for every workgroup"
         assert_same(got, want)
     counts = got[1]["tile_counts"]
     assert int(counts.sum()) == ntiles and int(counts[1 if shuffled else 0]) >= ntiles - 20

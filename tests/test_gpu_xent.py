@@ -149,6 +149,18 @@ def test_forward_and_backward_against_the_oracle(dtype, V, BK, gpu_device):
             check_against_oracle(l, tgt, eps, f"{dtype} V{V} B{BK[0]} K{BK[1]}", gpu_device)
 
 
+@pytest.mark.parametrize("V", [1025, 2048])
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_three_and_four_chunks_of_the_16_bit_types(dtype, V, gpu_device):
+    """A 16-bit chunk is 512 logits, so the V list above reaches one chunk, two (1000) and the online
+    and long forms (4097) for fp16 / bf16, never the three- and four-chunk in-register instantiation."""
+    BK = (3, 7)
+    l = randn4((*BK, V), DTYPES[dtype], gpu_device, seed=V)
+    for tgt in (random_tokens(BK, V, V + 7, gpu_device), random_coeffs(BK, V + 7, gpu_device)):
+        for eps in (0.0, 0.1):
+            check_against_oracle(l, tgt, eps, f"{dtype} V{V} B3 K7", gpu_device)
+
+
 # ------------------------------------------------------------------------- bitwise --
 def test_grid_stride_over_four_times_the_resident_rows(gpu_device):
     """Four times as many rows as a decode launch keeps resident (beast_logits_resident_rows: the

@@ -179,6 +179,7 @@ def test_option_constants_match_header():
     consts = {k[4:]: v for k, v in vars(_lib).items() if k.startswith("OPT_")}
     assert defs == consts
     assert defs["LAST_CODEC_LAUNCH"] == 8
+    assert defs["LAST_LAUNCH_GRID"] == 9
 
 
 def test_bpe_loop_constants_match_header():
@@ -209,6 +210,24 @@ def test_last_codec_launch_is_read_only_and_zero_before_any_launch():
         assert lib.beast_set_option(_lib.OPT_LAST_CODEC_LAUNCH, v) == _lib.BEAST_E_INVALID
         assert b"read-only" in lib.beast_last_error()
     assert lib.beast_get_option(_lib.OPT_LAST_CODEC_LAUNCH) == before
+
+
+def test_last_launch_grid_is_read_only_and_zero_before_any_launch():
+    """BEAST_OPT_LAST_LAUNCH_GRID reads 0 in a process that has launched nothing (a fresh one: this
+    process may have run GPU tests), and beast_set_option refuses it and leaves it as it was."""
+    import sys
+    code = ("from beast_tokenizer_amd import _lib; lib = _lib.load(); "
+            "print(lib.beast_get_option(_lib.OPT_LAST_LAUNCH_GRID), _lib.last_launch_grid())")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == ["0", "0"]
+    lib = _lib.load()
+    before = lib.beast_get_option(_lib.OPT_LAST_LAUNCH_GRID)
+    assert before >= 0
+    for v in (0, 1, before):
+        assert lib.beast_set_option(_lib.OPT_LAST_LAUNCH_GRID, v) == _lib.BEAST_E_INVALID
+        assert b"read-only" in lib.beast_last_error()
+    assert lib.beast_get_option(_lib.OPT_LAST_LAUNCH_GRID) == before
 
 
 def test_codec_launch_decoder_fields():
