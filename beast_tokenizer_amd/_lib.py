@@ -21,7 +21,7 @@ BEAST_E_INVALID = -1
 BEAST_E_HIP = -2
 BEAST_E_UNSUPPORTED = -3
 BEAST_E_WORKSPACE = -4
-ABI_VERSION = 5
+ABI_VERSION = 6
 OPT_GENERIC_KERNELS = 1
 OPT_BLOCK_WAVES = 2
 OPT_MERGE_LDS_MIN = 3
@@ -66,6 +66,10 @@ SIGNATURES = {
                                      _vp]),
     "beast_encode_windows_f32": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32,
                                         _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "beast_reconstruct_windows_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _vp,
+                                             _vp, _i64, _vp, _f32, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "beast_blend_candidates_host": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _vp]),
+    "beast_blend_member_host": (_i32, [_i64, _i64, _i64, _i32, _i64]),
     "beast_cond_fixed_f32": (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _i32,
                                     _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "beast_cond_add_f32": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -268,6 +268,16 @@ class BEASTBsplineBPETokenizer(BEASTBsplineTokenizer):
         out = (self._discrete_to_bpe(mp_tokens, as_tensors=return_tensors), params)
         return out + (mp_tokens,) if return_mp_tokens else out
 
+    def reconstruct_windows(self, ids: Iterable[TokenLike], starts: torch.Tensor, ends: torch.Tensor,
+                            num_frames: int, *, blend="uniform", fill: float = float("nan"),
+                            return_tile_counts: bool = False) -> tuple:
+        """The way back from ``encode_windows``: the BPE ids of a window table's chunks become MP tokens
+        (``bpe_to_mp_tokens``) and are blended into frames
+        (:meth:`BEASTBsplineTokenizer.reconstruct_windows`)."""
+        return BEASTBsplineTokenizer.reconstruct_windows(self, self.bpe_to_mp_tokens(ids), starts, ends, num_frames,
+                                                         blend=blend, fill=fill, respect_llm_vocab_size=False,
+                                                         return_tile_counts=return_tile_counts)
+
     def bpe_to_mp_tokens(self, tokens: Iterable[TokenLike]) -> torch.Tensor:
         """Convert BPE tokens back to discrete BEAST bins."""
         return self._bpe_to_discrete(tokens)

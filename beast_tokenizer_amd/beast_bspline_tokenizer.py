@@ -135,7 +135,7 @@ class _Plan:
 
     __slots__ = ("dev", "idx", "version", "wmin", "wmax", "keep", "T", "min_din", "dkey", "pinned",
                  "p_phi", "p_proj", "p_src", "p_dst", "p_wmn", "p_wmx", "enc", "rec", "fast", "fast_addr",
-                 "fast_enc", "fast_rec", "llm", "off", "enc_win")
+                 "fast_enc", "fast_rec", "llm", "off", "enc_win", "rec_win")
 
     def __init__(self, tok: "BEASTBsplineTokenizer", dev: torch.device):
         lib = _lib.load()
@@ -158,6 +158,7 @@ class _Plan:
         self.p_wmn, self.p_wmx = wmn.data_ptr(), wmx.data_ptr()
         self.enc, self.rec = lib.beast_encode_f32, lib.beast_reconstruct_f32
         self.enc_win = lib.beast_encode_windows_f32
+        self.rec_win = lib.beast_reconstruct_windows_f32
         fp = _fastpath()
         self.fast = self.fast_addr = self.fast_enc = self.fast_rec = None
         if fp is not None and not tok._conditioned:
@@ -1270,6 +1271,147 @@ class BEASTBsplineTokenizer(TokenizerBase):
         q = column_quantiles(allp, [0.01, 0.99], reduce)
         self.w_min.copy_(q[0].to(self.w_min.device))
         self.w_max.copy_(q[1].to(self.w_max.device))
+
+    # ===============================================
+    #   - blending window tokens back into frames -
+    # ===============================================
+
+    def blend_weights(self, kind="uniform", *, m=0.01, horizon=None):
+        """Blend weights for ``reconstruct_windows``: fp32 [seq_len] on the tokenizer's device, entry
+        ``t`` the weight of a window's sample ``t`` (the row ``t`` frames after the window's start).
+
+        ``"uniform"``: all ones, the plain mean of every chunk that covers a frame.
+        ``"exp"``: ``exp(m * (t - (seq_len - 1)))``.  On a stride-1 table the chunks covering a frame
+        are the ones predicted 0 .. seq_len-1 frames earlier and the oldest has the largest ``t``, so
+        after the normalisation this is ACT's temporal ensembling ``exp(-m * i)`` with ``i = 0`` the
+        oldest prediction; ``m > 0`` favours older chunks.  At table stride ``s`` consecutive chunks
+        are ``s`` samples apart, so ACT's ``m`` corresponds to ``m / s`` here.
+        ``"first"``: 1 for ``t < horizon``, else 0 -- the receding-horizon rule that executes the
+        first ``horizon`` steps of each chunk."""
+        T = int(self.times.numel())
+        t = torch.arange(T, dtype=torch.float64)
+        if kind == "uniform":
+            w = torch.ones(T, dtype=torch.float64)
+        elif kind == "exp":
+            w = torch.exp(float(m) * (t - (T - 1)))
+        elif kind == "first":
+            if horizon is None or not 1 <= int(horizon) <= T:
+                raise ValueError(f'blend_weights("first") needs 1 <= horizon <= seq_len={T}; got {horizon}')
+            w = (t < int(horizon)).to(torch.float64)
+        else:
+            raise ValueError(f'blend kind must be "uniform", "exp" or "first"; got {kind!r}')
+        return w.to(torch.float32).to(self.device)
+
+    def _blend_windows(self, tokens, ntokens, starts, ends, num_frames, blend, fill, offset: int, want_counts: bool):
+        """One launch of beast_reconstruct_windows_f32 (csrc/blend.hip).  The argument checks run before
+        the device is asked for."""
+        if self._basis.conditioned:
+            raise NotImplementedError(
+                "reconstruct_windows supports init_cond_order = end_cond_order = 0 only: the conditions are kept "
+                "per batch from y0, y1 of materialised trajectories (uni_bspline.py:499-550), and a window "
+                "table has none")
+        src = tokens if tokens is not None else ntokens
+        if not isinstance(src, torch.Tensor):
+            src = torch.as_tensor(src)
+        if src.dim() == 3:
+            src = src.reshape(src.shape[0], -1)
+        DN = self.num_basis * self.num_dof
+        if src.dim() != 2 or src.shape[1] != DN:
+            raise ValueError(f"tokens must be [W, num_basis*num_dof = {DN}] (or [W, num_basis, num_dof]); got "
+                             f"{tuple(src.shape)}")
+        if (tokens is not None) == src.dtype.is_floating_point or src.dtype is torch.bool:
+            raise ValueError(f"{'tokens must be integers' if tokens is not None else 'params must be floating point'}; "
+                             f"got {src.dtype}")
+        if not isinstance(starts, torch.Tensor):
+            starts = torch.as_tensor(starts)
+        if not isinstance(ends, torch.Tensor):
+            ends = torch.as_tensor(ends)
+        if (starts.dim() != 1 or starts.shape != ends.shape or starts.dtype is not torch.int64
+                or ends.dtype is not torch.int64):
+            raise ValueError(f"starts / ends must be int64 [W] tables of one length; got {tuple(starts.shape)} "
+                             f"{starts.dtype} and {tuple(ends.shape)} {ends.dtype}")
+        W = starts.shape[0]
+        if src.shape[0] != W:
+            raise ValueError(f"{src.shape[0]} token rows for a table of {W} windows")
+        R = int(num_frames)
+        if R < 0:
+            raise ValueError(f"num_frames must be >= 0; got {num_frames}")
+        # host tables are checked here; a device table is not synchronised on (the kernel clamps it)
+        if W and starts.device.type == "cpu" and ends.device.type == "cpu":
+            if bool(((starts < 0) | (starts >= ends) | (ends > R)).any()):
+                raise ValueError(f"window table out of range: need 0 <= start < end <= R={R} for every window")
+            if bool((starts[1:] < starts[:-1]).any()):
+                raise ValueError("window table is not sorted: starts must be non-decreasing (window_index builds "
+                                 "such a table)")
+        T = int(self.times.numel())
+        if isinstance(blend, str):
+            blend = self.blend_weights(blend)
+        elif not isinstance(blend, torch.Tensor):
+            blend = torch.as_tensor(blend, dtype=torch.float32)
+        if blend.shape != (T,) or not blend.dtype.is_floating_point:
+            raise ValueError(f"blend must be a floating-point [seq_len = {T}] tensor; got {tuple(blend.shape)} "
+                             f"{blend.dtype}")
+        if blend.device.type == "cpu" and not bool((torch.isfinite(blend) & (blend >= 0)).all()):
+            raise ValueError("blend weights must be finite and >= 0")
+        p = self._plan()
+        dev = p.dev
+        src = src.to(dev, dtype=torch.int64 if tokens is not None else torch.float32).contiguous()
+        starts, ends = starts.to(dev).contiguous(), ends.to(dev).contiguous()
+        blend = blend.to(dev, dtype=torch.float32).contiguous()
+        D = self.num_dof
+        frames = torch.empty((R, D), dtype=torch.float32, device=dev)
+        coverage = torch.empty((R,), dtype=torch.int32, device=dev)
+        weight = torch.empty((R,), dtype=torch.float32, device=dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev) if want_counts else None
+        if R:
+            # an empty tensor has no address to pass: an empty table's pointers are never read
+            none = torch.zeros(2, dtype=torch.int64, device=dev).data_ptr() if W == 0 else None
+            p_src = none or src.data_ptr()
+            rc = p.rec_win(p_src if tokens is not None else None, None if tokens is not None else p_src, W, D,
+                           self.joint_dof, self.num_basis, self.vocab_size, offset, p.p_wmn, p.p_wmx, p.p_phi, T,
+                           none or starts.data_ptr(), none or ends.data_ptr(), R, blend.data_ptr(), float(fill),
+                           p.p_dst, D, frames.data_ptr(), D, coverage.data_ptr(), weight.data_ptr(),
+                           None if counts is None else counts.data_ptr(), _lib.raw_stream(p.idx))
+            if rc:
+                _lib.check(rc, "beast_reconstruct_windows_f32")
+        info = {"coverage": coverage, "weight": weight}
+        if want_counts:
+            info["tile_counts"] = counts
+        return frames, info
+
+    @torch.no_grad()
+    def reconstruct_windows(self, tokens, starts, ends, num_frames, *, blend="uniform", fill=float("nan"),
+                            respect_llm_vocab_size=True, return_tile_counts=False):
+        """The way back from ``encode_windows``: blend the tokens of a window table into the frames of a
+        flat buffer, (frames fp32 [num_frames, num_dof], {"coverage": int32 [num_frames], "weight": fp32
+        [num_frames]}), from one launch of ``beast_reconstruct_windows_f32`` on the current stream --
+        no [W, seq_len, num_dof] intermediate and no atomics, so two runs agree bitwise.
+
+        ``tokens`` int [W, num_basis*num_dof] as ``encode_windows`` returns them; ``starts`` / ``ends``
+        int64 [W], the same table with the same meaning, and with non-decreasing starts
+        (:meth:`window_index` builds such a table): window ``w`` owns the frames ``starts[w] + t`` for
+        ``t < min(seq_len, ends[w] - starts[w])``; its edge-padding samples own nothing.  Frame ``r`` is
+        ``sum_k blend[t_k] y_k / sum_k blend[t_k]`` over the windows that own it, in table order, with
+        ``y_k`` bitwise ``reconstruct_traj``'s sample ``t_k = r - starts[w_k]`` of that window's tokens;
+        samples whose blend weight is 0 are skipped.  ``coverage`` counts the
+        contributors and ``weight`` is the denominator; frames nobody owns hold ``fill``.
+
+        ``blend``: ``"uniform"``, ``"exp"`` (:meth:`blend_weights`' defaults) or a [seq_len] tensor
+        (finite and >= 0: a host tensor is checked, a device tensor is not read back).  Host tables are
+        checked for range and order (``ValueError``); device tables are never synchronised on: the
+        kernel clamps them, so a bad one gives wrong numbers, never a fault.  ``return_tile_counts``
+        adds ``"tile_counts"``: int32 [2], the chunks of candidate windows the kernel's row tiles
+        walked / the tiles that walked more than one.  Tokenizers with init / end conditions raise
+        ``NotImplementedError``."""
+        return self._blend_windows(tokens, None, starts, ends, num_frames, blend, fill,
+                                   self._offset(respect_llm_vocab_size), return_tile_counts)
+
+    @torch.no_grad()
+    def reconstruct_windows_continuous(self, params, starts, ends, num_frames, *, blend="uniform",
+                                       fill=float("nan"), return_tile_counts=False):
+        """``reconstruct_windows`` from normalised params in [-1, 1] ((t d) order, as
+        ``encode_continuous_windows`` returns them and ``reconstruct_traj_continuous`` reads them)."""
+        return self._blend_windows(None, params, starts, ends, num_frames, blend, fill, 0, return_tile_counts)
 
     # ===============================================
     #           - tokenizer LLM tokenization -

@@ -236,13 +236,6 @@ int launch_rec_v(RecArgs a, const Queue& q) {
              : launch<k_reconstruct_v<KS, S, 0>>(grid, RV_WR * 64, L.total, q, "k_reconstruct_v", a.tokens, a.B, 8, v);
 }
 
-// Shared-basis positions run on the MFMA (k_reconstruct*) while the padded output tile fits LDS,
-// else in k_reconstruct_rows' sequential FMA order (k_roundtrip reproduces whichever applies).
-template <int TBT>
-bool rec_mfma_fits(int Tout, int D, int N, int ndo, int lut_n) {
-  return rec_smem<TBT, 4, 0>(Tout, D, N, ndo, 2, lut_n).total <= 112 * 1024;
-}
-
 template <int TBT>
 int launch_reconstruct(RecArgs a, int D, int nj, int N, bool shared, const Queue& q) {
   a.g = make_geom<TBT>(D, nj, N, 1);

@@ -125,6 +125,14 @@ __host__ __device__ inline RecSmem rec_smem(int Tout, int D, int N, int ndo, int
   return s;
 }
 
+// Shared-basis positions run on the MFMA (k_reconstruct*) while the padded output tile fits LDS,
+// else in k_reconstruct_rows' sequential FMA order (k_roundtrip and k_blend_windows reproduce
+// whichever applies).
+template <int TBT>
+inline bool rec_mfma_fits(int Tout, int D, int N, int ndo, int lut_n) {
+  return rec_smem<TBT, 4, 0>(Tout, D, N, ndo, 2, lut_n).total <= 112 * 1024;
+}
+
 // decode-only output (params_out, (d n) order) straight from the staged tokens
 template <int NT = NTHREADS>
 __device__ __forceinline__ void rec_params_out(const RecArgs& a, const unsigned char* tokl, int64_t b0, int nb,

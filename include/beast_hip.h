@@ -41,8 +41,10 @@ extern "C" {
 #define BEAST_E_UNSUPPORTED (-3) /* shape outside the kernels' envelope       */
 #define BEAST_E_WORKSPACE (-4)   /* workspace too small                       */
 
-#define BEAST_ABI_VERSION 5   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
-                                 4: beast_score_rows, beast_score_rows_bwd; 5: beast_encode_windows_f32 */
+#define BEAST_ABI_VERSION 6   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
+                                 4: beast_score_rows, beast_score_rows_bwd; 5: beast_encode_windows_f32;
+                                 6: beast_reconstruct_windows_f32, beast_blend_candidates_host,
+                                    beast_blend_member_host */
 
 int beast_abi_version(void);
 const char* beast_last_error(void);
@@ -227,6 +229,65 @@ int beast_encode_windows_f32(const float* frames, int64_t R, int64_t sr, int64_t
                              int D, int n_joint, const int32_t* dof_src, const float* proj, int N,
                              const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
                              float* params_out, int64_t* tokens_out, uint32_t* tile_counts, void* windows_stream);
+
+/* The way back: blend the tokens of a window table into the rows of a flat [R] frame buffer, one
+ * launch, no [W][T][D] intermediate and no atomic on an output.
+ *   win_start, win_end  DEVICE int64 [W], the table beast_encode_windows_f32 takes, same meaning:
+ *                       window w has rows_w = min(T, end_w - start_w) real samples, sample t < rows_w
+ *                       lies on row start_w + t; samples t >= rows_w are edge padding and contribute
+ *                       to nothing.  REQUIRED: win_start is non-decreasing (equal starts allowed).
+ *   tokens              int64 [W][N*D] in (n d) order, tok_offset subtracted first; or
+ *   ntokens             fp32 normalised [W][N*D] in [-1, 1], as beast_reconstruct_f32 reads them
+ *                       (exactly one of the two is given)
+ *   basis               [2][T][N] fp32, the default-grid basis per kind; w_min / w_max, dof_dst,
+ *                       num_dof_out as in beast_reconstruct_f32
+ *   blend               fp32 [T], finite and >= 0: the weight of sample index t
+ * y_w(t, d) is window w's reconstruction: coefficients decoded bit-exactly as beast_reconstruct_f32
+ * decodes them, then ONE fma chain over the N basis functions starting from 0 against the basis
+ * row of the DoF's kind, in the order beast_reconstruct_f32 sums them for the same N, T, D,
+ * num_dof_out and token form (on the matrix cores n = k*KS + ks for ks = 0 .. KS-1, k = 0 .. 3 with
+ * KS = ceil(N/4); n ascending where that entry point takes its per-row kernel), so y_w(t, d) is
+ * bitwise what beast_reconstruct_f32 writes for window w's tokens alone.  For row r and DoF d let
+ * w_1 < w_2 < ... < w_C be the windows, in TABLE ORDER, with start_w <= r < start_w + rows_w and
+ * blend[r - start_w] != 0, and t_k = r - start_{w_k}:
+ *     num = 0; den = 0
+ *     for k = 1 .. C:  num = fmaf(blend[t_k], y_{w_k}(t_k, d), num);  den = den + blend[t_k]
+ *     frames_out[r*out_sr + dof_dst[d]] = C > 0 ? num / den (IEEE division) : fill
+ *     coverage_out[r] = C (int32)        weight_out[r] = den (fp32; 0 where C = 0)
+ * A sample whose blend weight is 0 is skipped, not multiplied (a NaN there does not propagate).  The
+ * columns of frames_out[r][0 .. num_dof_out) dof_dst does not name are written 0; every element of
+ * the three outputs is written (they may be uninitialised).  A row's value depends only on its own
+ * contributors and their table order: not on R, W, the tiling or the rest of the table, and two
+ * runs agree bitwise.
+ * The tables are not trusted: starts are clamped into [0, R-1] and ends into [start+1, R] as
+ * beast_encode_windows_f32 clamps them, and the candidate search reads table indices in [0, W)
+ * only, so a bad device table (out of range, or not sorted: windows are then missed) gives wrong
+ * numbers, never a fault.
+ *   coverage_out, weight_out  nullable
+ *   tile_counts  nullable uint32[2], zeroed by the caller: per tile of output rows, [0] += the
+ *                chunks of candidate windows walked, [1] += 1 if more than one; for tests and tools.
+ * BEAST_E_INVALID: a null required pointer, both or neither of tokens / ntokens, W < 0, R < 0,
+ * T < 1, N < 1, D < 1, n_joint outside [0, D], num_dof_out < D, out_sr < num_dof_out, tokens with
+ * vocab < 2.  BEAST_E_UNSUPPORTED outside N <= 16, T <= 256, D <= 64, num_dof_out <= 4096.
+ * R == 0 is a no-op; W == 0 with R > 0 is not (every row gets fill, 0, 0; the table and token
+ * pointers are then never read).  The stream parameter is the header's `stream` in every respect. */
+int beast_reconstruct_windows_f32(const int64_t* tokens, const float* ntokens, int64_t W, int D, int n_joint,
+                                  int N, int vocab, int64_t tok_offset, const float* w_min, const float* w_max,
+                                  const float* basis, int T, const int64_t* win_start, const int64_t* win_end,
+                                  int64_t R, const float* blend, float fill, const int32_t* dof_dst,
+                                  int num_dof_out, float* frames_out, int64_t out_sr, int32_t* coverage_out,
+                                  float* weight_out, uint32_t* tile_counts, void* blend_stream);
+
+/* Host only, no GPU: beast_reconstruct_windows_f32's index logic (csrc/blend_index.h) over HOST
+ * arrays, for tests.  beast_blend_candidates_host: the half-open range [a, b) of windows that can
+ * own a row of [r0, r1), 0 <= r0 <= r1 <= R: a is the first w whose (clamped) start exceeds r0 - T,
+ * b the first whose start is >= r1, by binary search; 0 <= *a_out <= *b_out <= W and every table
+ * index read lies in [0, W) whatever the table holds (win_end is part of the table but no search
+ * reads it).  beast_blend_member_host: the sample index t in [0, T) as which the window
+ * (start, end), clamped, owns row r, or -1 where it does not (or R < 1, T < 1). */
+int beast_blend_candidates_host(const int64_t* win_start, const int64_t* win_end, int64_t W, int64_t R, int T,
+                                int64_t r0, int64_t r1, int64_t* a_out, int64_t* b_out);
+int beast_blend_member_host(int64_t start, int64_t end, int64_t R, int T, int64_t r);
 
 /* ------------------------------------------------------------- H6 - H8 ---
  * Replaces BEASTBsplineTokenizer.decode + reconstruct_traj (beast/
