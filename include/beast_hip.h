@@ -693,9 +693,12 @@ int beast_bpe_pretok_emit(const int64_t* tok, const int64_t* seq_off, int64_t n_
 int beast_bpe_count_pairs(const uint16_t* sym, const uint32_t* wstart, const uint32_t* wlen,
                           const uint32_t* wcount, int64_t n_words, uint32_t* table, int Vt, int n_sym,
                           void* stream);
-/* sig[w] = OR over word w's symbols x of two bits of x (a 64-bit Bloom mask, csrc/bpe_common.h
- * sig_bit).  The merges use it to skip words that cannot contain a pair without reading their
- * symbols, and keep it current for the words they rewrite. */
+/* sig[w] = word w's 64-bit Bloom signature (csrc/bpe_common.h sig_of): the low 32 bits hold its
+ * symbols, two bits each (sig_sym), the high 32 its adjacent pairs, two bits each from one hash of
+ * the pair (sig_pair); a word of no symbols has signature 0.  A word can hold the adjacent pair
+ * (a, b) only if it has every bit of sig_need(a, b) = sig_sym(a) | sig_sym(b) | sig_pair(a, b): the
+ * merges skip the other words without reading their symbols, and keep sig current for the words
+ * they rewrite. */
 int beast_bpe_word_signatures(const uint16_t* sym, const uint32_t* wstart, const uint32_t* wlen, int64_t n_words,
                               uint64_t* sig, void* stream);
 
