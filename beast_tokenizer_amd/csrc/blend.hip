@@ -347,7 +347,7 @@ extern "C" int beast_reconstruct_windows_f32(const int64_t* tokens, const float*
                                              const float* blend, float fill, const int32_t* dof_dst,
                                              int num_dof_out, float* frames_out, int64_t out_sr,
                                              int32_t* coverage_out, float* weight_out, uint32_t* tile_counts,
-                                             void* blend_stream) {
+                                             void* stream) {
   const char* fn = "beast_reconstruct_windows_f32";
   BEAST_REQUIRE(w_min && w_max && basis && blend && dof_dst, "%s: null input pointer", fn);
   BEAST_REQUIRE(W >= 0 && R >= 0, "%s: need W >= 0 and R >= 0 (W=%lld R=%lld)", fn, (long long)W, (long long)R);
@@ -382,7 +382,7 @@ extern "C" int beast_reconstruct_windows_f32(const int64_t* tokens, const float*
   const int lds = blend_smem(T, D, N, num_dof_out, n_joint < D ? 2 : 1, a.cw).total;
   BEAST_REQUIRE_CODE(lds <= 160 * 1024, BEAST_E_UNSUPPORTED, "%s: a tile needs %d B of LDS", fn, lds);
   Queue q;
-  BEAST_TRY(queue_of(blend_stream, q, fn));
+  BEAST_TRY(queue_of(stream, q, fn));
   if (BL_S * D <= 4 * NTHREADS) return launch_blend_t<4>(a, lds, q);
   if (BL_S * D <= 8 * NTHREADS) return launch_blend_t<8>(a, lds, q);
   return launch_blend_t<16>(a, lds, q);

@@ -2133,7 +2133,7 @@ int run_score_typed(int dtype, bool backward, const ScoreArgs& a, bool trunc, co
 extern "C" int beast_sample_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                                  float temperature, int top_k, float top_p, const float* uniforms, int S,
                                  int64_t tok_offset, int64_t* tokens_out, float* logprob_out, int32_t* kept_out,
-                                 void* sample_stream) {
+                                 void* stream) {
   BEAST_TRY(check_common("beast_sample_rows", logits, dtype, B, K, V, sb, sk, temperature));
   BEAST_REQUIRE(top_k >= 0, "beast_sample_rows: top_k must be >= 0 (got %d)", top_k);
   BEAST_REQUIRE(top_p > 0.0f && top_p <= 1.0f, "beast_sample_rows: top_p must lie in (0, 1] (got %g)", (double)top_p);
@@ -2152,7 +2152,7 @@ extern "C" int beast_sample_rows(const void* logits, int dtype, int64_t B, int K
   a.u = uniforms; a.S = S; a.tok_offset = tok_offset;
   a.tok = tokens_out; a.logprob = logprob_out; a.kept = kept_out;
   Queue q;
-  if (const int rc = queue_of(sample_stream, q, "beast_sample_rows")) return rc;
+  if (const int rc = queue_of(stream, q, "beast_sample_rows")) return rc;
   switch (dtype) {
     case BEAST_LOGITS_F32: return run_sample<ElemF32>(a, trunc, q);
     case BEAST_LOGITS_F16: return run_sample<ElemF16>(a, trunc, q);
@@ -2164,7 +2164,7 @@ extern "C" int beast_score_rows(const void* logits, int dtype, int64_t B, int K,
                                 const void* ref_logits, int64_t rsb, int64_t rsk, float temperature, int top_k,
                                 float top_p, const int64_t* tokens, int S, int64_t tok_offset, int64_t ignore_index,
                                 float* logprob_out, float* entropy_out, float* kl_out, int32_t* kept_out,
-                                float* stats_out, void* score_stream) {
+                                float* stats_out, void* stream) {
   const char* fn = "beast_score_rows";
   bool trunc = false;
   BEAST_TRY(check_score(fn, logits, dtype, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
@@ -2177,7 +2177,7 @@ extern "C" int beast_score_rows(const void* logits, int dtype, int64_t B, int K,
                            tok_offset, ignore_index);
   a.logprob = logprob_out; a.entropy = entropy_out; a.kl = kl_out; a.kept = kept_out; a.stats = stats_out;
   Queue q;
-  if (const int rc = queue_of(score_stream, q, fn)) return rc;
+  if (const int rc = queue_of(stream, q, fn)) return rc;
   return run_score_typed(dtype, false, a, trunc, q);
 }
 
@@ -2186,7 +2186,7 @@ extern "C" int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, in
                                     float top_p, const int64_t* tokens, int S, int64_t tok_offset,
                                     int64_t ignore_index, const float* stats, const float* grad_logprob,
                                     const float* grad_entropy, const float* grad_kl, void* grad_logits, int64_t gsb,
-                                    int64_t gsk, void* score_stream) {
+                                    int64_t gsk, void* stream) {
   const char* fn = "beast_score_rows_bwd";
   bool trunc = false;
   BEAST_TRY(check_score(fn, logits, dtype, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
@@ -2203,13 +2203,13 @@ extern "C" int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, in
   a.stats = const_cast<float*>(stats); a.g_lp = grad_logprob; a.g_h = grad_entropy; a.g_kl = grad_kl;
   a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk; a.gK = folded_k(B, K, gsb, gsk);
   Queue q;
-  if (const int rc = queue_of(score_stream, q, fn)) return rc;
+  if (const int rc = queue_of(stream, q, fn)) return rc;
   return run_score_typed(dtype, true, a, trunc, q);
 }
 
 extern "C" int beast_logits_expect(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                                    float temperature, int64_t tok_offset, float* mean_out, int64_t* argmax_out,
-                                   float* stats_out, void* hip_stream) {
+                                   float* stats_out, void* stream) {
   BEAST_TRY(check_common("beast_logits_expect", logits, dtype, B, K, V, sb, sk, temperature));
   BEAST_REQUIRE(mean_out || argmax_out || stats_out, "beast_logits_expect: no output requested");
   if (B == 0) return BEAST_OK;
@@ -2218,14 +2218,14 @@ extern "C" int beast_logits_expect(const void* logits, int dtype, int64_t B, int
   a.inv_tau = (float)(1.0 / (double)temperature); a.vm1 = (float)(V - 1); a.tok_offset = tok_offset;
   a.mean = mean_out; a.amax = argmax_out; a.stats = stats_out;
   Queue q;
-  if (const int rc = queue_of(hip_stream, q, "beast_logits_expect")) return rc;
+  if (const int rc = queue_of(stream, q, "beast_logits_expect")) return rc;
   return run_typed(dtype, false, a, q, nullptr);
 }
 
 extern "C" int beast_logits_expect_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                                        float temperature, const float* mean, const float* stats,
                                        const float* grad_mean, void* grad_logits, int64_t gsb, int64_t gsk,
-                                       void* hip_stream) {
+                                       void* stream) {
   BEAST_TRY(check_common("beast_logits_expect_bwd", logits, dtype, B, K, V, sb, sk, temperature));
   BEAST_REQUIRE(mean && stats && grad_mean && grad_logits, "beast_logits_expect_bwd: null pointer");
   BEAST_REQUIRE(gsb >= 0 && gsk >= V, "beast_logits_expect_bwd: grad_logits rows must not overlap (gsb=%lld, "
@@ -2238,11 +2238,11 @@ extern "C" int beast_logits_expect_bwd(const void* logits, int dtype, int64_t B,
   a.mean = const_cast<float*>(mean); a.stats = const_cast<float*>(stats);
   a.grad_mean = grad_mean; a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk;
   Queue q;
-  if (const int rc = queue_of(hip_stream, q, "beast_logits_expect_bwd")) return rc;
+  if (const int rc = queue_of(stream, q, "beast_logits_expect_bwd")) return rc;
   return run_typed(dtype, true, a, q, nullptr);
 }
 
-extern "C" int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* hip_stream) {
+extern "C" int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* stream) {
   BEAST_REQUIRE(dtype == BEAST_LOGITS_F32 || dtype == BEAST_LOGITS_F16 || dtype == BEAST_LOGITS_BF16,
                 "beast_logits_resident_rows: unknown dtype code %d", dtype);
   BEAST_REQUIRE_CODE(V >= LG_MIN_V && V <= LG_MAX_V, BEAST_E_UNSUPPORTED,
@@ -2250,7 +2250,7 @@ extern "C" int64_t beast_logits_resident_rows(int dtype, int V, int backward, vo
   LogitsArgs a{};
   a.V = V;
   Queue q;
-  if (const int rc = queue_of(hip_stream, q, "beast_logits_resident_rows")) return rc;
+  if (const int rc = queue_of(stream, q, "beast_logits_resident_rows")) return rc;
   int64_t rows = 0;
   if (const int rc = run_typed(dtype, backward != 0, a, q, &rows)) return rc;
   return rows;
@@ -2259,14 +2259,14 @@ extern "C" int64_t beast_logits_resident_rows(int dtype, int V, int backward, vo
 extern "C" int beast_xent_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                                const int64_t* target_tok, const float* target_pos, int64_t tok_offset,
                                int64_t ignore_index, float smoothing, float* loss_out, float* stats_out,
-                               int64_t* argmax_out, void* queue_stream) {
+                               int64_t* argmax_out, void* stream) {
   BEAST_TRY(check_xent("beast_xent_rows", logits, dtype, B, K, V, sb, sk, target_tok, target_pos, smoothing));
   BEAST_REQUIRE(loss_out || stats_out || argmax_out, "beast_xent_rows: no output requested");
   if (B == 0) return BEAST_OK;
   XentArgs a = xent_args(logits, B, K, V, sb, sk, target_tok, target_pos, tok_offset, ignore_index, smoothing);
   a.loss = loss_out; a.stats = stats_out; a.amax = argmax_out;
   Queue q;
-  if (const int rc = queue_of(queue_stream, q, "beast_xent_rows")) return rc;
+  if (const int rc = queue_of(stream, q, "beast_xent_rows")) return rc;
   return run_xent_typed(dtype, false, a, q);
 }
 
@@ -2274,7 +2274,7 @@ extern "C" int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int
                                    const int64_t* target_tok, const float* target_pos, int64_t tok_offset,
                                    int64_t ignore_index, float smoothing, const float* stats,
                                    const float* grad_loss, void* grad_logits, int64_t gsb, int64_t gsk,
-                                   void* queue_stream) {
+                                   void* stream) {
   BEAST_TRY(check_xent("beast_xent_rows_bwd", logits, dtype, B, K, V, sb, sk, target_tok, target_pos, smoothing));
   BEAST_REQUIRE(stats && grad_loss && grad_logits, "beast_xent_rows_bwd: null pointer");
   BEAST_REQUIRE(gsb >= 0 && gsk >= V, "beast_xent_rows_bwd: grad_logits rows must not overlap (gsb=%lld, "
@@ -2284,6 +2284,6 @@ extern "C" int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int
   a.gK = folded_k(B, K, gsb, gsk);
   a.stats = const_cast<float*>(stats); a.grad_loss = grad_loss; a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk;
   Queue q;
-  if (const int rc = queue_of(queue_stream, q, "beast_xent_rows_bwd")) return rc;
+  if (const int rc = queue_of(stream, q, "beast_xent_rows_bwd")) return rc;
   return run_xent_typed(dtype, true, a, q);
 }

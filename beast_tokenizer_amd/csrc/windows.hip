@@ -229,7 +229,7 @@ extern "C" int beast_encode_windows_f32(const float* frames, int64_t R, int64_t 
                                         int n_joint, const int32_t* dof_src, const float* proj, int N,
                                         const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
                                         float* params_out, int64_t* tokens_out, uint32_t* tile_counts,
-                                        void* windows_stream) {
+                                        void* stream) {
   BEAST_REQUIRE(frames && win_start && win_end && dof_src && proj, "beast_encode_windows_f32: null input pointer");
   BEAST_REQUIRE(params_out || tokens_out, "beast_encode_windows_f32: no output requested");
   BEAST_REQUIRE(W >= 0, "beast_encode_windows_f32: window count W=%lld must be >= 0", (long long)W);
@@ -259,6 +259,6 @@ extern "C" int beast_encode_windows_f32(const float* frames, int64_t R, int64_t 
   w.win_end = reinterpret_cast<const long long*>(win_end);
   w.tile_counts = tile_counts;
   Queue q;
-  BEAST_TRY(queue_of(windows_stream, q, "beast_encode_windows_f32"));
+  BEAST_TRY(queue_of(stream, q, "beast_encode_windows_f32"));
   return launch_windows(w, T, D, n_joint, N, q);
 }

@@ -222,13 +222,12 @@ int beast_encode_rows_f32(const float* traj, int64_t B, int T, int64_t sb, int64
  * BEAST_E_INVALID: a null required pointer, both outputs null, R < 1 with W > 0, W < 0, T < 1,
  * N < 1, D < 1, row_elems < 1, n_joint outside [0, D], a negative stride, overlapping rows,
  * tokens_out with vocab < 2 or without bounds.  BEAST_E_UNSUPPORTED outside beast_encode_f32's
- * envelope: N <= 16, T <= 256, D <= 64.  W == 0 is a no-op.  The stream parameter is the header's
- * `stream` in every respect. */
+ * envelope: N <= 16, T <= 256, D <= 64.  W == 0 is a no-op. */
 int beast_encode_windows_f32(const float* frames, int64_t R, int64_t sr, int64_t sd, int row_elems,
                              const int64_t* win_start, const int64_t* win_end, int64_t W, int T,
                              int D, int n_joint, const int32_t* dof_src, const float* proj, int N,
                              const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
-                             float* params_out, int64_t* tokens_out, uint32_t* tile_counts, void* windows_stream);
+                             float* params_out, int64_t* tokens_out, uint32_t* tile_counts, void* stream);
 
 /* The way back: blend the tokens of a window table into the rows of a flat [R] frame buffer, one
  * launch, no [W][T][D] intermediate and no atomic on an output.
@@ -270,13 +269,13 @@ int beast_encode_windows_f32(const float* frames, int64_t R, int64_t sr, int64_t
  * T < 1, N < 1, D < 1, n_joint outside [0, D], num_dof_out < D, out_sr < num_dof_out, tokens with
  * vocab < 2.  BEAST_E_UNSUPPORTED outside N <= 16, T <= 256, D <= 64, num_dof_out <= 4096.
  * R == 0 is a no-op; W == 0 with R > 0 is not (every row gets fill, 0, 0; the table and token
- * pointers are then never read).  The stream parameter is the header's `stream` in every respect. */
+ * pointers are then never read). */
 int beast_reconstruct_windows_f32(const int64_t* tokens, const float* ntokens, int64_t W, int D, int n_joint,
                                   int N, int vocab, int64_t tok_offset, const float* w_min, const float* w_max,
                                   const float* basis, int T, const int64_t* win_start, const int64_t* win_end,
                                   int64_t R, const float* blend, float fill, const int32_t* dof_dst,
                                   int num_dof_out, float* frames_out, int64_t out_sr, int32_t* coverage_out,
-                                  float* weight_out, uint32_t* tile_counts, void* blend_stream);
+                                  float* weight_out, uint32_t* tile_counts, void* stream);
 
 /* Host only, no GPU: beast_reconstruct_windows_f32's index logic (csrc/blend_index.h) over HOST
  * arrays, for tests.  beast_blend_candidates_host: the half-open range [a, b) of windows that can
@@ -402,7 +401,7 @@ int beast_reconstruct_derivs_bwd_f32(const float* grad_pos, const float* grad_ve
  * One wave owns a row; element v always belongs to lane (v / (16 / sizeof(T))) % 64 and every sum
  * has an order fixed by (V, dtype) alone -- no atomics, no LDS -- so a row's outputs are bitwise
  * identical alone or in any batch, at any alignment, in any grid and from run to run.
- * hip_stream is the `stream` of the conventions above.  Envelope: 2 <= V <= 65536, else
+ * Envelope: 2 <= V <= 65536, else
  * BEAST_E_UNSUPPORTED; temperature must be finite and > 0; B = 0 returns 0 without a launch. */
 #define BEAST_LOGITS_F32 0
 #define BEAST_LOGITS_F16 1
@@ -412,18 +411,18 @@ int beast_logits_expect(const void* logits, int dtype, int64_t B, int K, int V,
                         int64_t sb, int64_t sk,
                         float temperature, int64_t tok_offset,
                         float* mean_out, int64_t* argmax_out, float* stats_out,
-                        void* hip_stream);
+                        void* stream);
 
 int beast_logits_expect_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                             float temperature, const float* mean, const float* stats,
                             const float* grad_mean,
                             void* grad_logits, int64_t gsb, int64_t gsk,
-                            void* hip_stream);
+                            void* stream);
 
 /* Rows that one launch of beast_logits_expect (backward != 0: of beast_logits_expect_bwd) keeps
  * resident on the stream's device for this dtype and V: a launch over more rows walks them with a
  * grid stride.  Launches nothing.  Returns the count (> 0) or a negative BEAST_E_* code. */
-int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* hip_stream);
+int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* stream);
 
 /* Train a discrete head from its logits: the cross-entropy of a token row against a token, or
  * against the TWO-HOT target of an unquantised normalised coefficient, and its gradient.  The
@@ -461,20 +460,20 @@ int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* hip_str
  *                of every row is written and nothing around it.
  * Rows, lanes and sums are those of beast_logits_expect: a row's outputs are bitwise identical
  * alone or in any batch, at any alignment, in any grid and from run to run.
- * queue_stream is the `stream` of the conventions above.  Envelope: 2 <= V <= 65536, else
+ * Envelope: 2 <= V <= 65536, else
  * BEAST_E_UNSUPPORTED; B = 0 returns 0 without a launch. */
 int beast_xent_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                     const int64_t* target_tok, const float* target_pos,
                     int64_t tok_offset, int64_t ignore_index, float smoothing,
                     float* loss_out, float* stats_out, int64_t* argmax_out,
-                    void* queue_stream);
+                    void* stream);
 
 int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                         const int64_t* target_tok, const float* target_pos,
                         int64_t tok_offset, int64_t ignore_index, float smoothing,
                         const float* stats, const float* grad_loss,
                         void* grad_logits, int64_t gsb, int64_t gsk,
-                        void* queue_stream);
+                        void* stream);
 
 /* Draw tokens from a discrete head's logits: S inverse-CDF draws per row under
  * softmax(l / temperature), optionally truncated to the top-k and then the top-p (nucleus) bins,
@@ -503,7 +502,7 @@ int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, 
  *   kept_out     nullable [B][K] int32
  * Rows, lanes and sums are those of beast_logits_expect: a row's outputs are bitwise identical alone
  * or in any batch, at any alignment, in any grid and from run to run, and draw s depends on u_s only.
- * sample_stream is the `stream` of the conventions above.  Envelope: 2 <= V <= 65536 and
+ * Envelope: 2 <= V <= 65536 and
  * 1 <= S <= 64; a truncation (1 <= top_k < V or top_p < 1) only for rows of up to four chunks
  * (V <= 1,024 fp32, V <= 2,048 fp16 / bf16 -- BEAST vocabularies are 256), else BEAST_E_UNSUPPORTED.
  * temperature finite and > 0, top_k >= 0, 0 < top_p <= 1; B = 0 returns 0 without a launch. */
@@ -511,7 +510,7 @@ int beast_sample_rows(const void* logits, int dtype, int64_t B, int K, int V, in
                       float temperature, int top_k, float top_p,
                       const float* uniforms, int S, int64_t tok_offset,
                       int64_t* tokens_out, float* logprob_out, int32_t* kept_out,
-                      void* sample_stream);
+                      void* stream);
 
 /* Score tokens under a discrete head's logits: the log-probability of S given tokens per row, the
  * entropy of the row's distribution and its divergence from a reference row, with the gradient of
@@ -561,7 +560,7 @@ int beast_sample_rows(const void* logits, int dtype, int64_t B, int K, int V, in
  *                 of every row is written and nothing around it.
  * Rows, lanes and sums are those of beast_logits_expect: a row's outputs are bitwise identical alone
  * or in any batch, at any alignment, in any grid and from run to run.
- * score_stream is the `stream` of the conventions above.  Envelope: beast_sample_rows' -- 2 <= V <=
+ * Envelope: beast_sample_rows' -- 2 <= V <=
  * 65536 and 0 <= S <= 64; a truncation (1 <= top_k < V or top_p < 1) only for rows of up to four
  * chunks (V <= 1,024 fp32, V <= 2,048 fp16 / bf16), else BEAST_E_UNSUPPORTED.  temperature finite
  * and > 0, top_k >= 0, 0 < top_p <= 1; B = 0 returns 0 without a launch. */
@@ -570,7 +569,7 @@ int beast_score_rows(const void* logits, int dtype, int64_t B, int K, int V, int
                      float temperature, int top_k, float top_p,
                      const int64_t* tokens, int S, int64_t tok_offset, int64_t ignore_index,
                      float* logprob_out, float* entropy_out, float* kl_out, int32_t* kept_out, float* stats_out,
-                     void* score_stream);
+                     void* stream);
 
 int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                          const void* ref_logits, int64_t rsb, int64_t rsk,
@@ -579,7 +578,7 @@ int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V,
                          const float* stats,
                          const float* grad_logprob, const float* grad_entropy, const float* grad_kl,
                          void* grad_logits, int64_t gsb, int64_t gsk,
-                         void* score_stream);
+                         void* stream);
 
 /* Error statistics of encode -> reconstruct in ONE launch: how well the tokenizer represents the
  * trajectories, and whether the spline fit or the quantiser is to blame.  traj .. dof_src, proj,

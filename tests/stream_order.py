@@ -1,5 +1,6 @@
-"""The ordering probe of tests/test_gpu_stream_order.py: does a call do ALL its device work, in order,
-on the stream it is given?
+"""The ordering probe of the tests/test_gpu_*stream_order.py modules: does a call do ALL its device
+work, in order, on the stream it is given?  Below the probe, what those modules share: the case
+registries, the two test bodies, the canary, the fault guard and the logits-family helpers.
 
 A case names the buffers a call reads (each with a ``good`` and a ``stale`` content of the same shape),
 the buffers it writes or uses as scratch, and the call itself.  ``probe`` then
@@ -28,17 +29,22 @@ outputs or scratch.
 """
 from __future__ import annotations
 
+import functools
 import time
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple
 
+import numpy as np
+import pytest
 import torch
+
+from beast_tokenizer_amd import BEASTBsplineTokenizer, _lib
 
 MIN_DELAY_MS = 10.0     # the delay of a case: max(MIN_DELAY_MS, HOST_FACTOR * host time of the call) ...
 HOST_FACTOR = 20.0      # ... the factor is headroom for host jitter
 MAX_DELAY_MS = 99.0     # no single delay reaches 100 ms
 
-# what the module learned about the machine (test_gpu_stream_order prints it at the end)
+# what the probe learned about the machine (the canary fixture prints it when a module ends)
 MEASURED = {"cycles_per_ms": None, "max_host_ms": 0.0, "max_host_case": None, "max_delay_ms": 0.0}
 
 
@@ -254,3 +260,141 @@ def assert_ordered(case: Case, dev: torch.device, api: bool = False) -> Report:
     assert r.ordered, (f"{case.name}: result tensors {r.mismatch} differ from the null-stream result: part of the "
                        f"call did not run in order on the stream it was given ({case.entries})")
     return r
+
+
+# ------------------------------------------------------------------- registries --
+CASES = {}        # section A: id -> (registering module, entry points, builder(dev) -> Case)
+API_CASES = {}    # section B: id -> (registering module, builder(dev) -> Case)
+
+
+def capi(cid, *entries):
+    def deco(fn):
+        assert cid not in CASES
+        CASES[cid] = (fn.__module__, entries, fn)
+        return fn
+    return deco
+
+
+def api(cid):
+    def deco(fn):
+        assert cid not in API_CASES
+        API_CASES[cid] = (fn.__module__, fn)
+        return fn
+    return deco
+
+
+def ids(registry, module):
+    """The ids that ``module`` registered: a module parametrises its tests over its own cases."""
+    return sorted(cid for cid, item in registry.items() if item[0] == module)
+
+
+# ------------------------------------------------------------------ fault guard --
+_FAULT = []       # the message of a HIP error met in this process: nothing more is started after one
+
+
+def stops_after_a_fault(fn):
+    """A HIP fault is sticky: once a HIP error has been seen in any stream-order test, every later one,
+    in any module, fails at once instead of launching more work on a faulted device."""
+    @functools.wraps(fn)
+    def wrapper(*args, **kw):
+        if _FAULT:
+            pytest.fail(f"not run: a HIP error was met earlier in a stream-order test ({_FAULT[0][:200]})")
+        try:
+            return fn(*args, **kw)
+        except (RuntimeError, _lib.BeastError) as e:
+            if "HIP error" in str(e) or "illegal memory access" in str(e) or "hipError" in str(e):
+                _FAULT.append(str(e))
+            raise
+    return wrapper
+
+
+# ------------------------------------------------------------------ test bodies --
+@stops_after_a_fault
+def check_capi(cid, dev):
+    """Section A: the entry point gets the side stream's handle while torch's current stream is the
+    null stream, so any internal use of the current stream or of stream 0 shows."""
+    _, entries, build = CASES[cid]
+    case = build(dev)
+    case.entries = entries
+    assert_ordered(case, dev)
+
+
+@stops_after_a_fault
+def check_api(cid, dev):
+    """Section B: the same probe with ``s`` current: _lib.stream_of / raw_stream, the C++ fast path's
+    stream query and the handles captured at construction all have to resolve to ``s``."""
+    assert_ordered(API_CASES[cid][1](dev), dev, api=True)
+
+
+# ----------------------------------------------------------------------- canary --
+@stops_after_a_fault
+def canary_report(dev):
+    """The probe on a deliberately mis-ordered torch-only call: ``out.copy_(inp)`` issued on the
+    null stream whatever stream it is given."""
+    good = torch.arange(1, 4097, dtype=torch.float32, device=dev)
+    stale = torch.zeros_like(good)
+    inp, out = torch.empty_like(good), torch.empty_like(good)
+    null = torch.cuda.default_stream(dev)
+
+    def call(_handle):
+        with torch.cuda.stream(null):
+            out.copy_(inp)
+        return [out]
+    return probe(Case("canary", ("torch copy on the null stream",), [(inp, good, stale)], call, scratch=[out]), dev)
+
+
+_CANARY = {}      # "report": computed once per process; "printed": the figures last printed
+
+
+@pytest.fixture(scope="module", autouse=True)
+def canary(gpu_device):
+    """Every test of a stream-order module needs the canary: if the probe calls a mis-ordered copy
+    "ordered" (a side stream that blocks on the null stream, say), no other result means anything,
+    so all fail.  Each module imports this fixture; the report is shared."""
+    if "report" not in _CANARY:
+        _CANARY["report"] = canary_report(gpu_device)
+    r = _CANARY["report"]
+    if not (r.busy and r.mismatch):
+        pytest.fail(f"canary: a copy on the null stream was reported as ordered on the side stream "
+                    f"(busy={r.busy}, mismatch={r.mismatch}): the probe cannot see a mis-ordering here")
+    yield r
+    m = MEASURED
+    if _CANARY.get("printed") != m:       # a module that raised no figure repeats no line
+        _CANARY["printed"] = dict(m)
+        print(f"\nstream-order probe: {m['cycles_per_ms']:.0f} sleep cycles/ms; largest host time "
+              f"{m['max_host_ms']:.3f} ms ({m['max_host_case']}); largest delay {m['max_delay_ms']:.1f} ms")
+
+
+# --------------------------------------------- the logits family's case helpers --
+FLOOR = 16 * 2.0 ** -24
+
+
+def logits(shape, dtype, dev, seed):
+    gen = torch.Generator().manual_seed(seed)
+    return (torch.randn(shape, generator=gen) * 4.0).to(dtype).to(dev)
+
+
+def f64(t):
+    return t.detach().to("cpu", torch.float64).numpy()
+
+
+def close(got, want, rel=0.0):
+    fin = np.isfinite(want)
+    assert np.array_equal(np.isneginf(want), np.isneginf(got))
+    scale = max(1.0, float(np.abs(want[fin]).max()))
+    assert np.all(np.abs(got[fin] - want[fin]) <= 4 * FLOOR * scale + rel * np.abs(want[fin]))
+
+
+def api_tok(dev, init=None):
+    """A default-shaped tokenizer whose plan is built and complete; ``init(tok)`` runs before the plan."""
+    tok = BEASTBsplineTokenizer(num_dof=14, num_basis=10, seq_len=50, vocab_size=256, device=str(dev))
+    if init is not None:
+        init(tok)
+    tok._plan()
+    torch.cuda.synchronize(dev)
+    return tok
+
+
+def api_case(name, good, fn, check=None):
+    x = torch.empty_like(good)
+    return Case(name, (name,), [(x, good, good.flip(0).contiguous())], lambda h: fn(x), check_expected=check)

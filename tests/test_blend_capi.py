@@ -17,7 +17,7 @@ def blend_args(**kw):
     a = dict(tokens=FAKE, ntokens=None, W=4, D=14, n_joint=12, N=10, vocab=256, tok_offset=0, w_min=FAKE, w_max=FAKE,
              basis=FAKE, T=50, win_start=FAKE, win_end=FAKE, R=1000, blend=FAKE, fill=float("nan"), dof_dst=FAKE,
              num_dof_out=14, frames_out=FAKE, out_sr=14, coverage_out=FAKE, weight_out=FAKE, tile_counts=FAKE,
-             blend_stream=None)
+             stream=None)
     assert set(kw) <= set(a)
     a.update(kw)
     return list(a.values())

@@ -5,20 +5,14 @@ section A   beast_reconstruct_windows_f32 with the side stream's handle while to
             is the null stream, from tokens and from normalised tokens; the tokens have a good and a
             stale content, the window tables are never stale (they are indices);
 section B   reconstruct_windows and reconstruct_windows_continuous under ``torch.cuda.stream(s)``.
-
-The entry point spells its stream parameter ``void* blend_stream`` (it is the header's ``stream`` in
-every respect), so the accounting tests of the older stream-order files do not see it;
-``test_every_blend_stream_export_is_probed`` below does that accounting for every prototype that
-takes a ``blend_stream``.
 """
-import re
-
 import pytest
 import torch
 
 import blend_oracle as BO
-from stream_order import Case, assert_ordered
-from test_lib_exports import HEADER, header_decls
+import stream_order as SO
+from stream_order import Case, api, capi
+from stream_order import canary  # noqa: F401 (autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,9 +21,6 @@ from beast_tokenizer_amd import BEASTBsplineTokenizer, _lib  # noqa: E402
 PROBED = ["beast_reconstruct_windows_f32"]
 R, T, D, N = 1200, 50, 7, 10
 EPS = 2.0 ** -24
-
-CASES = {}        # id -> (entry points, builder(dev) -> Case): section A
-API_CASES = {}    # section B
 
 
 def make_tok(dev):
@@ -89,20 +80,13 @@ def raw_case(name, dev, normalised):
                 check_expected=check_expected(tok, good, s, e, bw, normalised))
 
 
-def capi(cid, normalised):
-    CASES[cid] = (tuple(PROBED), lambda dev: raw_case(cid, dev, normalised))
+capi("reconstruct_windows[tokens]", *PROBED)(lambda dev: raw_case("reconstruct_windows[tokens]", dev, False))
+capi("reconstruct_windows[ntokens]", *PROBED)(lambda dev: raw_case("reconstruct_windows[ntokens]", dev, True))
 
 
-capi("reconstruct_windows[tokens]", False)
-capi("reconstruct_windows[ntokens]", True)
-
-
-@pytest.mark.parametrize("cid", sorted(CASES))
+@pytest.mark.parametrize("cid", SO.ids(SO.CASES, __name__))
 def test_capi_is_ordered_on_the_given_stream(cid, gpu_device):
-    entries, build = CASES[cid]
-    case = build(gpu_device)
-    case.entries = entries
-    assert_ordered(case, gpu_device)
+    SO.check_capi(cid, gpu_device)
 
 
 # ================================================================== B. the Python API ==
@@ -121,24 +105,10 @@ def api_case(name, dev, normalised):
     return Case(name, (name,), [(x, good, stale)], fn, check_expected=check_expected(tok, good, s, e, bw, normalised))
 
 
-API_CASES["reconstruct_windows"] = lambda dev: api_case("reconstruct_windows", dev, False)
-API_CASES["reconstruct_windows_continuous"] = lambda dev: api_case("reconstruct_windows_continuous", dev, True)
+api("reconstruct_windows")(lambda dev: api_case("reconstruct_windows", dev, False))
+api("reconstruct_windows_continuous")(lambda dev: api_case("reconstruct_windows_continuous", dev, True))
 
 
-@pytest.mark.parametrize("cid", sorted(API_CASES))
+@pytest.mark.parametrize("cid", SO.ids(SO.API_CASES, __name__))
 def test_python_api_is_ordered_on_the_current_stream(cid, gpu_device):
-    assert_ordered(API_CASES[cid](gpu_device), gpu_device, api=True)
-
-
-def test_every_blend_stream_export_is_probed():
-    """Every prototype of include/beast_hip.h whose stream parameter is spelled ``blend_stream`` has a
-    section-A case, and the module docstring names them all."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    takes = {m.group(1) for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-             if re.search(r"void\s*\*\s*blend_stream\b", m.group(2))}
-    assert takes <= set(header_decls())
-    assert takes == set(PROBED), sorted(takes)
-    covered = {e for entries, _ in CASES.values() for e in entries}
-    assert covered == set(PROBED)
-    for name in takes:
-        assert re.search(rf"\b{name}\b", __doc__), f"{name} is missing from the module docstring"
+    SO.check_api(cid, gpu_device)

@@ -7,59 +7,24 @@ section A   beast_logits_expect and beast_logits_expect_bwd with the side stream
 section B   expected_params_from_logits, reconstruct_traj_from_logits, greedy_tokens_from_logits and
             the autograd backward under ``torch.cuda.stream(s)``.
 
-The two entry points spell their stream parameter ``void* hip_stream``, so
-test_every_stream_export_is_accounted_for of tests/test_gpu_stream_order.py does not see them;
-``test_every_logits_stream_export_is_probed`` below does that accounting for every
-``beast_logits_*`` prototype that takes a ``hip_stream``.
-
 launches nothing (a query; it only asks the stream for its device)
     beast_logits_resident_rows
 """
-import re
-
 import numpy as np
 import pytest
 import torch
 
 import logits_oracle as LO
-from stream_order import Case, assert_ordered
-from test_lib_exports import HEADER, header_decls
+import stream_order as SO
+from stream_order import FLOOR, Case, api, api_case, api_tok, capi, f64, logits
+from stream_order import canary  # noqa: F401 (autouse)
 
 pytestmark = pytest.mark.gpu
 
-from beast_tokenizer_amd import BEASTBsplineTokenizer, _lib  # noqa: E402
+from beast_tokenizer_amd import _lib  # noqa: E402
 
-FLOOR = 16 * 2.0 ** -24
 PROBED = ["beast_logits_expect", "beast_logits_expect_bwd"]
 NO_LAUNCH = {"beast_logits_resident_rows": "a query: asks the stream for its device and launches nothing"}
-
-CASES = {}        # id -> (entry points, builder(dev) -> Case): section A
-API_CASES = {}    # section B
-
-
-def capi(cid, *entries):
-    def deco(fn):
-        assert cid not in CASES
-        CASES[cid] = (entries, fn)
-        return fn
-    return deco
-
-
-def api(cid):
-    def deco(fn):
-        assert cid not in API_CASES
-        API_CASES[cid] = fn
-        return fn
-    return deco
-
-
-def logits(shape, dtype, dev, seed):
-    gen = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=gen) * 4.0).to(dtype).to(dev)
-
-
-def f64(t):
-    return t.detach().to("cpu", torch.float64).numpy()
 
 
 def raw_case(name, dev, dtype, strided):
@@ -109,34 +74,26 @@ def _(dev):
     return raw_case("logits_expect+bwd[bf16-strided]", dev, torch.bfloat16, True)
 
 
-@pytest.mark.parametrize("cid", sorted(CASES))
+@pytest.mark.parametrize("cid", SO.ids(SO.CASES, __name__))
 def test_capi_is_ordered_on_the_given_stream(cid, gpu_device):
-    entries, build = CASES[cid]
-    case = build(gpu_device)
-    case.entries = entries
-    assert_ordered(case, gpu_device)
+    SO.check_capi(cid, gpu_device)
 
 
 # ================================================================== B. the Python API ==
-def api_tok(dev):
-    tok = BEASTBsplineTokenizer(num_dof=14, num_basis=10, seq_len=50, vocab_size=256, device=str(dev))
-    gen = torch.Generator().manual_seed(9)
-    tok.w_min.copy_(-1.0 - torch.rand(140, generator=gen))
-    tok.w_max.copy_(1.0 + torch.rand(140, generator=gen))
-    tok._plan()
+def decode_tok(dev):
+    def bounds(tok):
+        gen = torch.Generator().manual_seed(9)
+        tok.w_min.copy_(-1.0 - torch.rand(140, generator=gen))
+        tok.w_max.copy_(1.0 + torch.rand(140, generator=gen))
+    tok = api_tok(dev, bounds)
     tok._basis.deriv_constants(tok.times.to(dev, torch.float32).reshape(-1), tok._times_version)
     torch.cuda.synchronize(dev)          # the cached constants are not what this module probes
     return tok
 
 
-def api_case(name, good, fn, check=None):
-    x = torch.empty_like(good)
-    return Case(name, (name,), [(x, good, good.flip(0).contiguous())], lambda h: fn(x), check_expected=check)
-
-
 @api("expected_params_from_logits")
 def _(dev):
-    tok = api_tok(dev)
+    tok = decode_tok(dev)
     good = logits((9, 140, 256), torch.bfloat16, dev, seed=3)
 
     def check(exp):
@@ -149,7 +106,7 @@ def _(dev):
 
 @api("reconstruct_traj_from_logits")
 def _(dev):
-    tok = api_tok(dev)
+    tok = decode_tok(dev)
     good = logits((9, 10, 14, 256), torch.float32, dev, seed=4)
 
     def fn(x):
@@ -163,7 +120,7 @@ def _(dev):
 
 @api("greedy_tokens_from_logits")
 def _(dev):
-    tok = api_tok(dev)
+    tok = decode_tok(dev)
     tok.set_llm_vocab_size(1000)
     good = logits((9, 140, 1000), torch.float16, dev, seed=5)
 
@@ -176,7 +133,7 @@ def _(dev):
 def _(dev):
     """Forward and ``.backward()``: both backward launches ask for the current stream when autograd
     runs them (on the forward's stream), so the gradient is part of the probed sequence."""
-    tok = api_tok(dev)
+    tok = decode_tok(dev)
     good = logits((9, 140, 256), torch.float32, dev, seed=6)
     gup = torch.randn((9, 50, 14), device=dev, generator=torch.Generator(dev).manual_seed(7))
 
@@ -192,22 +149,6 @@ def _(dev):
     return api_case("reconstruct_traj_from_logits[backward]", good, fn, check)
 
 
-@pytest.mark.parametrize("cid", sorted(API_CASES))
+@pytest.mark.parametrize("cid", SO.ids(SO.API_CASES, __name__))
 def test_python_api_is_ordered_on_the_current_stream(cid, gpu_device):
-    assert_ordered(API_CASES[cid](gpu_device), gpu_device, api=True)
-
-
-def test_every_logits_stream_export_is_probed():
-    """Every ``beast_logits_*`` prototype of include/beast_hip.h that takes a ``hip_stream`` has a
-    section-A case or is listed, with its reason, as launching nothing; the module docstring names
-    them all; and no other prototype uses that spelling to stay out of the older accounting."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    takes = {m.group(1) for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-             if re.search(r"void\s*\*\s*hip_stream\b", m.group(2))}
-    assert takes <= set(header_decls())
-    assert takes == {n for n in header_decls() if n.startswith("beast_logits_")}, sorted(takes)
-    assert set(PROBED) | set(NO_LAUNCH) == takes and not set(PROBED) & set(NO_LAUNCH)
-    covered = {e for entries, _ in CASES.values() for e in entries}
-    assert covered == set(PROBED)
-    for name in takes:
-        assert re.search(rf"\b{name}\b", __doc__), f"{name} is missing from the module docstring"
+    SO.check_api(cid, gpu_device)

@@ -6,57 +6,21 @@ section A   beast_sample_rows with the side stream's handle while torch's curren
             with top-k and top-p; the logits and the uniforms are both inputs with a stale content;
 section B   sample_tokens_from_logits under ``torch.cuda.stream(s)``: with the caller's uniforms, and
             with a generator, where the ``torch.rand`` the method issues is part of the probed sequence.
-
-The entry point spells its stream parameter ``void* sample_stream`` (it is the header's
-``stream`` in every respect), so the accounting tests of tests/test_gpu_stream_order.py,
-tests/test_gpu_logits_stream_order.py and tests/test_gpu_xent_stream_order.py do not see it;
-``test_every_sample_stream_export_is_probed`` below does that accounting for every prototype that
-takes a ``sample_stream``.
 """
-import re
-
 import numpy as np
 import pytest
 import torch
 
 import sample_oracle as SO
-from stream_order import Case, assert_ordered
-from test_lib_exports import HEADER, header_decls
+import stream_order
+from stream_order import FLOOR, Case, api, api_case, api_tok, capi, f64, logits
+from stream_order import canary  # noqa: F401 (autouse)
 
 pytestmark = pytest.mark.gpu
 
-from beast_tokenizer_amd import BEASTBsplineTokenizer, _lib  # noqa: E402
+from beast_tokenizer_amd import _lib  # noqa: E402
 
-FLOOR = 16 * 2.0 ** -24
 PROBED = ["beast_sample_rows"]
-
-CASES = {}        # id -> (entry points, builder(dev) -> Case): section A
-API_CASES = {}    # section B
-
-
-def capi(cid, *entries):
-    def deco(fn):
-        assert cid not in CASES
-        CASES[cid] = (entries, fn)
-        return fn
-    return deco
-
-
-def api(cid):
-    def deco(fn):
-        assert cid not in API_CASES
-        API_CASES[cid] = fn
-        return fn
-    return deco
-
-
-def logits(shape, dtype, dev, seed):
-    gen = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=gen) * 4.0).to(dtype).to(dev)
-
-
-def f64(t):
-    return t.detach().to("cpu", torch.float64).numpy()
 
 
 def check_draws(l64, u64, tok, lp, tau, top_k, top_p, off=0):
@@ -113,27 +77,12 @@ def _(dev):
     return raw_case("sample_rows[bf16-strided-top-k-top-p]", dev, torch.bfloat16, True, 50, 0.9)
 
 
-@pytest.mark.parametrize("cid", sorted(CASES))
+@pytest.mark.parametrize("cid", stream_order.ids(stream_order.CASES, __name__))
 def test_capi_is_ordered_on_the_given_stream(cid, gpu_device):
-    entries, build = CASES[cid]
-    case = build(gpu_device)
-    case.entries = entries
-    assert_ordered(case, gpu_device)
+    stream_order.check_capi(cid, gpu_device)
 
 
 # ================================================================== B. the Python API ==
-def api_tok(dev):
-    tok = BEASTBsplineTokenizer(num_dof=14, num_basis=10, seq_len=50, vocab_size=256, device=str(dev))
-    tok._plan()
-    torch.cuda.synchronize(dev)
-    return tok
-
-
-def api_case(name, good, fn, check=None):
-    x = torch.empty_like(good)
-    return Case(name, (name,), [(x, good, good.flip(0).contiguous())], lambda h: fn(x), check_expected=check)
-
-
 @api("sample_tokens_from_logits[uniforms]")
 def _(dev):
     tok = api_tok(dev)
@@ -169,20 +118,6 @@ def _(dev):
     return api_case("sample_tokens_from_logits[generator]", good, fn, check)
 
 
-@pytest.mark.parametrize("cid", sorted(API_CASES))
+@pytest.mark.parametrize("cid", stream_order.ids(stream_order.API_CASES, __name__))
 def test_python_api_is_ordered_on_the_current_stream(cid, gpu_device):
-    assert_ordered(API_CASES[cid](gpu_device), gpu_device, api=True)
-
-
-def test_every_sample_stream_export_is_probed():
-    """Every prototype of include/beast_hip.h whose stream parameter is spelled ``sample_stream`` has a
-    section-A case, and the module docstring names them all."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    takes = {m.group(1) for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-             if re.search(r"void\s*\*\s*sample_stream\b", m.group(2))}
-    assert takes <= set(header_decls())
-    assert takes == set(PROBED), sorted(takes)
-    covered = {e for entries, _ in CASES.values() for e in entries}
-    assert covered == set(PROBED)
-    for name in takes:
-        assert re.search(rf"\b{name}\b", __doc__), f"{name} is missing from the module docstring"
+    stream_order.check_api(cid, gpu_device)

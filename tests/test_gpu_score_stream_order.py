@@ -7,65 +7,23 @@ section A   beast_score_rows and beast_score_rows_bwd with the side stream's han
             and the tokens are all inputs with a stale content;
 section B   score_tokens_from_logits under ``torch.cuda.stream(s)``: the forward alone, and the forward
             with ``.backward()``.
-
-The entry points spell their stream parameter ``void* score_stream`` (it is the header's
-``stream`` in every respect), so the accounting tests of the four older stream-order files do not see
-them; ``test_every_score_stream_export_is_probed`` below does that accounting for every prototype that
-takes a ``score_stream``.
 """
-import re
-
 import numpy as np
 import pytest
 import torch
 
 import sample_oracle as SO
 import score_oracle as SC
-from stream_order import Case, assert_ordered
-from test_lib_exports import HEADER, header_decls
+import stream_order
+from stream_order import Case, api, api_case, api_tok, capi, close, f64, logits
+from stream_order import canary  # noqa: F401 (autouse)
 
 pytestmark = pytest.mark.gpu
 
-from beast_tokenizer_amd import BEASTBsplineTokenizer, _lib  # noqa: E402
+from beast_tokenizer_amd import _lib  # noqa: E402
 from beast_tokenizer_amd.beast_bspline_tokenizer import SCORE_STATS  # noqa: E402
 
-FLOOR = 16 * 2.0 ** -24
 PROBED = ["beast_score_rows", "beast_score_rows_bwd"]
-
-CASES = {}        # id -> (entry points, builder(dev) -> Case): section A
-API_CASES = {}    # section B
-
-
-def capi(cid, *entries):
-    def deco(fn):
-        assert cid not in CASES
-        CASES[cid] = (entries, fn)
-        return fn
-    return deco
-
-
-def api(cid):
-    def deco(fn):
-        assert cid not in API_CASES
-        API_CASES[cid] = fn
-        return fn
-    return deco
-
-
-def logits(shape, dtype, dev, seed):
-    gen = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=gen) * 4.0).to(dtype).to(dev)
-
-
-def f64(t):
-    return t.detach().to("cpu", torch.float64).numpy()
-
-
-def close(got, want, rel=0.0):
-    fin = np.isfinite(want)
-    assert np.array_equal(np.isneginf(want), np.isneginf(got))
-    scale = max(1.0, float(np.abs(want[fin]).max()))
-    assert np.all(np.abs(got[fin] - want[fin]) <= 4 * FLOOR * scale + rel * np.abs(want[fin]))
 
 
 def check_scores(l64, r64, tok, tau, top_k, top_p, off, lp, H, D, kept=None, grad=None, g=None, rel=0.0):
@@ -132,27 +90,12 @@ def _(dev):
     return raw_case("score_rows+bwd[bf16-strided-top-k-top-p-ref]", dev, torch.bfloat16, True, 50, 0.9, True)
 
 
-@pytest.mark.parametrize("cid", sorted(CASES))
+@pytest.mark.parametrize("cid", stream_order.ids(stream_order.CASES, __name__))
 def test_capi_is_ordered_on_the_given_stream(cid, gpu_device):
-    entries, build = CASES[cid]
-    case = build(gpu_device)
-    case.entries = entries
-    assert_ordered(case, gpu_device)
+    stream_order.check_capi(cid, gpu_device)
 
 
 # ================================================================== B. the Python API ==
-def api_tok(dev):
-    tok = BEASTBsplineTokenizer(num_dof=14, num_basis=10, seq_len=50, vocab_size=256, device=str(dev))
-    tok._plan()
-    torch.cuda.synchronize(dev)
-    return tok
-
-
-def api_case(name, good, fn, check=None):
-    x = torch.empty_like(good)
-    return Case(name, (name,), [(x, good, good.flip(0).contiguous())], lambda h: fn(x), check_expected=check)
-
-
 @api("score_tokens_from_logits")
 def _(dev):
     tok = api_tok(dev)
@@ -192,20 +135,6 @@ def _(dev):
     return api_case("score_tokens_from_logits[backward]", good, fn, check)
 
 
-@pytest.mark.parametrize("cid", sorted(API_CASES))
+@pytest.mark.parametrize("cid", stream_order.ids(stream_order.API_CASES, __name__))
 def test_python_api_is_ordered_on_the_current_stream(cid, gpu_device):
-    assert_ordered(API_CASES[cid](gpu_device), gpu_device, api=True)
-
-
-def test_every_score_stream_export_is_probed():
-    """Every prototype of include/beast_hip.h whose stream parameter is spelled ``score_stream`` has a
-    section-A case, and the module docstring names them all."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    takes = {m.group(1) for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-             if re.search(r"void\s*\*\s*score_stream\b", m.group(2))}
-    assert takes <= set(header_decls())
-    assert takes == set(PROBED), sorted(takes)
-    covered = {e for entries, _ in CASES.values() for e in entries}
-    assert covered == set(PROBED)
-    for name in takes:
-        assert re.search(rf"\b{name}\b", __doc__), f"{name} is missing from the module docstring"
+    stream_order.check_api(cid, gpu_device)

@@ -11,14 +11,17 @@ submission order, and late in a long test process a new stream often shares the 
 
 Two canaries guard the probe itself: a torch copy issued on the null stream, and two library
 calls (a kernel, an internal memset) handed the null stream, must all be REPORTED as mis-ordered.
-If the first is not, every test of the module fails.
+If the first is not, every test of every stream-order module fails (the ``canary`` fixture of
+tests/stream_order.py, computed once per process).  After a HIP error in any of those modules no
+later stream-order test starts GPU work (``stops_after_a_fault``).
 
 Section A calls the C-ABI with the side stream's handle while torch's current stream is the null
 stream; section B calls the Python API under ``torch.cuda.stream(s)``; section C builds the cached
 constants on one stream behind a delay and uses them at once from two others.
 
-The ``extern "C"`` functions that take a ``void* stream`` (``test_every_stream_export_is_accounted_for``
-checks this list against include/beast_hip.h):
+The ``extern "C"`` functions that take a ``void* stream`` and are not probed in one of the six
+sibling modules (tests/test_stream_order_accounting.py checks the lists of all seven against
+include/beast_hip.h):
 
 probed
     beast_bspline_basis_f32  beast_bspline_basis_deriv_f32  beast_bspline_projection_f64
@@ -46,7 +49,6 @@ not probed
 """
 import ctypes
 import json
-import re
 
 import numpy as np
 import pytest
@@ -57,9 +59,8 @@ import roundtrip_oracle
 import rows_oracle as RO
 import stream_order as SO
 from conftest import CONFIGS, load_json, load_npz
-from stream_order import Case, assert_ordered, probe
+from stream_order import CASES, Case, api, canary, capi, probe, stops_after_a_fault  # noqa: F401 (canary: autouse)
 from test_deriv_bwd_oracle import make_inputs
-from test_lib_exports import HEADER, header_decls
 
 pytestmark = pytest.mark.gpu
 
@@ -95,46 +96,6 @@ NOT_PROBED = {
     "beast_bpe_train_comm": "beast_bpe_train plus collectives, one host thread per rank; comm == NULL is beast_bpe_train",
 }
 
-_FAULT = []       # the message of a HIP error met in this module: nothing more is started after one
-
-
-def stops_after_a_fault(fn):
-    """A HIP fault is sticky: once a HIP error has been seen, the module's remaining tests fail at
-    once instead of launching more work on a faulted device."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(*args, **kw):
-        if _FAULT:
-            pytest.fail(f"not run: a HIP error was met earlier in this module ({_FAULT[0][:200]})")
-        try:
-            return fn(*args, **kw)
-        except (RuntimeError, _lib.BeastError) as e:
-            if "HIP error" in str(e) or "illegal memory access" in str(e) or "hipError" in str(e):
-                _FAULT.append(str(e))
-            raise
-    return wrapper
-
-
-CASES = {}        # id -> (entry points, builder(dev) -> Case): section A
-API_CASES = {}    # section B
-
-
-def capi(cid, *entries):
-    def deco(fn):
-        assert cid not in CASES
-        CASES[cid] = (entries, fn)
-        return fn
-    return deco
-
-
-def api(cid):
-    def deco(fn):
-        assert cid not in API_CASES
-        API_CASES[cid] = fn
-        return fn
-    return deco
-
 
 def dv(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -158,40 +119,6 @@ def run(name, *args):
 
 
 # ------------------------------------------------------------------------ canary --
-def canary_report(dev):
-    """The probe on a deliberately mis-ordered torch-only call: ``out.copy_(inp)`` issued on the
-    null stream whatever stream it is given."""
-    good = torch.arange(1, 4097, dtype=torch.float32, device=dev)
-    stale = torch.zeros_like(good)
-    inp, out = buf_like(good), buf_like(good)
-    null = torch.cuda.default_stream(dev)
-
-    def call(_handle):
-        with torch.cuda.stream(null):
-            out.copy_(inp)
-        return [out]
-    return probe(Case("canary", ("torch copy on the null stream",), [(inp, good, stale)], call, scratch=[out]), dev)
-
-
-_CANARY = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def canary(gpu_device):
-    """Every test of the module needs the canary: if the probe calls a mis-ordered copy "ordered" (a
-    side stream that blocks on the null stream, say), no other result means anything, so all fail."""
-    if "report" not in _CANARY:
-        _CANARY["report"] = canary_report(gpu_device)
-    r = _CANARY["report"]
-    if not (r.busy and r.mismatch):
-        pytest.fail(f"canary: a copy on the null stream was reported as ordered on the side stream "
-                    f"(busy={r.busy}, mismatch={r.mismatch}): the probe cannot see a mis-ordering here")
-    yield r
-    m = SO.MEASURED
-    print(f"\nstream-order probe: {m['cycles_per_ms']:.0f} sleep cycles/ms; largest host time "
-          f"{m['max_host_ms']:.3f} ms ({m['max_host_case']}); largest delay {m['max_delay_ms']:.1f} ms")
-
-
 def test_canary_reports_a_mismatch(canary):
     """The mis-ordered copy ran while the delay was still running (busy) and the snapshot is not the
     expected copy of the good input: it is the poison the side stream wrote afterwards."""
@@ -202,36 +129,17 @@ def test_canary_reports_a_mismatch(canary):
 
 
 @pytest.mark.parametrize("cid", ["quantize[mode0-tokens]", "bspline_basis_deriv[order2-above-degree-memset]"])
+@stops_after_a_fault
 def test_probe_sees_an_entry_point_on_the_wrong_stream(cid, gpu_device):
     """The same canary through the library: a kernel (k_quantize) and an internal memset (the
     order > degree branch of beast_bspline_basis_deriv_f32) handed the NULL stream while the probe
     drives the side stream.  The kernel reads the stale input, the memset is overwritten by the
     poison: both must be reported, or a wrong stream inside the library would go unseen too."""
-    case = CASES[cid][1](gpu_device)
+    case = CASES[cid][2](gpu_device)
     inner = case.call
     case.call = lambda _handle: inner(None)
     r = probe(case, gpu_device)
     assert r.busy and r.mismatch, (cid, r.busy, r.mismatch)
-
-
-def test_every_stream_export_is_accounted_for():
-    """Every prototype of include/beast_hip.h with a ``void* stream`` parameter is in exactly one of
-    the three groups of the module docstring, every probed one has a case, and the docstring names
-    them all: a new entry point cannot dodge the probe."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    takes_stream = {m.group(1) for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-                    if re.search(r"void\s*\*\s*stream\b", m.group(2))}
-    assert takes_stream <= set(header_decls()) and len(takes_stream) >= 40
-    groups = [set(PROBED), set(SYNCHRONOUS), set(NOT_PROBED)]
-    assert sum(len(g) for g in groups) == len(set().union(*groups)), "an entry point is in two groups"
-    assert set().union(*groups) == takes_stream, (sorted(takes_stream - set().union(*groups)),
-                                                  sorted(set().union(*groups) - takes_stream))
-    covered = {e for entries, _ in CASES.values() for e in entries}
-    assert covered == set(PROBED) | set(SYNCHRONOUS), (sorted((set(PROBED) | set(SYNCHRONOUS)) - covered),
-                                                       sorted(covered - set(PROBED) - set(SYNCHRONOUS)))
-    for name in takes_stream:
-        assert re.search(rf"\b{name}\b", __doc__), f"{name} is missing from the module docstring"
-    assert all(n.startswith("beast_comm_") or n == "beast_bpe_train_comm" for n in NOT_PROBED)
 
 
 # ================================================================= A. codec (k3 shapes) ==
@@ -1530,15 +1438,9 @@ def _(dev):
                 synchronous=True)
 
 
-@pytest.mark.parametrize("cid", sorted(CASES))
-@stops_after_a_fault
+@pytest.mark.parametrize("cid", SO.ids(CASES, __name__))
 def test_capi_is_ordered_on_the_given_stream(cid, gpu_device):
-    """Section A: the entry point gets the side stream's handle while torch's current stream is the
-    null stream, so any internal use of the current stream or of stream 0 shows."""
-    entries, build = CASES[cid]
-    case = build(gpu_device)
-    case.entries = entries
-    assert_ordered(case, gpu_device)
+    SO.check_capi(cid, gpu_device)
 
 
 # ================================================================== B. the Python API ==
@@ -1863,12 +1765,9 @@ def _(dev):
                     lambda x: [column_quantiles(x, [0.01, 0.99], ops=ops)], check)
 
 
-@pytest.mark.parametrize("cid", sorted(API_CASES))
-@stops_after_a_fault
+@pytest.mark.parametrize("cid", SO.ids(SO.API_CASES, __name__))
 def test_python_api_is_ordered_on_the_current_stream(cid, gpu_device):
-    """Section B: the same probe with ``s`` current: _lib.stream_of / raw_stream, the C++ fast path's
-    stream query and the handles captured at construction all have to resolve to ``s``."""
-    assert_ordered(API_CASES[cid](gpu_device), gpu_device, api=True)
+    SO.check_api(cid, gpu_device)
 
 
 # ===================================================== C. constants built on another stream ==

@@ -6,20 +6,14 @@ section A   beast_encode_windows_f32 with the side stream's handle while torch's
             shuffled (tiles gather); the frames have a good and a stale content, the window tables
             are never stale (they are indices);
 section B   encode_windows under ``torch.cuda.stream(s)``, plain and with ``update_bounds``.
-
-The entry point spells its stream parameter ``void* windows_stream`` (it is the header's ``stream`` in
-every respect), so the accounting tests of the older stream-order files do not see it;
-``test_every_windows_stream_export_is_probed`` below does that accounting for every prototype that
-takes a ``windows_stream``.
 """
-import re
-
 import pytest
 import torch
 
 import windows_oracle as WO
-from stream_order import Case, assert_ordered
-from test_lib_exports import HEADER, header_decls
+import stream_order as SO
+from stream_order import Case, api, capi
+from stream_order import canary  # noqa: F401 (autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,25 +21,6 @@ from beast_tokenizer_amd import BEASTBsplineTokenizer, _lib  # noqa: E402
 
 PROBED = ["beast_encode_windows_f32"]
 R, T, D, N = 1200, 50, 7, 10
-
-CASES = {}        # id -> (entry points, builder(dev) -> Case): section A
-API_CASES = {}    # section B
-
-
-def capi(cid, *entries):
-    def deco(fn):
-        assert cid not in CASES
-        CASES[cid] = (entries, fn)
-        return fn
-    return deco
-
-
-def api(cid):
-    def deco(fn):
-        assert cid not in API_CASES
-        API_CASES[cid] = fn
-        return fn
-    return deco
 
 
 def make_tok(dev, wide_bounds=True):
@@ -117,12 +92,9 @@ def _(dev):
     return raw_case("encode_windows[shuffled]", dev, True)
 
 
-@pytest.mark.parametrize("cid", sorted(CASES))
+@pytest.mark.parametrize("cid", SO.ids(SO.CASES, __name__))
 def test_capi_is_ordered_on_the_given_stream(cid, gpu_device):
-    entries, build = CASES[cid]
-    case = build(gpu_device)
-    case.entries = entries
-    assert_ordered(case, gpu_device)
+    SO.check_capi(cid, gpu_device)
 
 
 # ================================================================== B. the Python API ==
@@ -158,20 +130,6 @@ def _(dev):
     return api_case("encode_windows[update_bounds]", dev, update_bounds=True)
 
 
-@pytest.mark.parametrize("cid", sorted(API_CASES))
+@pytest.mark.parametrize("cid", SO.ids(SO.API_CASES, __name__))
 def test_python_api_is_ordered_on_the_current_stream(cid, gpu_device):
-    assert_ordered(API_CASES[cid](gpu_device), gpu_device, api=True)
-
-
-def test_every_windows_stream_export_is_probed():
-    """Every prototype of include/beast_hip.h whose stream parameter is spelled ``windows_stream`` has a
-    section-A case, and the module docstring names them all."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    takes = {m.group(1) for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-             if re.search(r"void\s*\*\s*windows_stream\b", m.group(2))}
-    assert takes <= set(header_decls())
-    assert takes == set(PROBED), sorted(takes)
-    covered = {e for entries, _ in CASES.values() for e in entries}
-    assert covered == set(PROBED)
-    for name in takes:
-        assert re.search(rf"\b{name}\b", __doc__), f"{name} is missing from the module docstring"
+    SO.check_api(cid, gpu_device)

@@ -17,16 +17,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "beast_hip.h")
 
 
-def header_decls():
-    """name -> parameter count, parsed from the prototypes in include/beast_hip.h."""
+def header_protos():
+    """name -> parameter list (the text between the parentheses) of the prototypes in include/beast_hip.h."""
     txt = open(HEADER).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     txt = re.sub(r"//[^\n]*", "", txt)
-    out = {}
-    for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S):
-        args = m.group(2).strip()
-        out[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
-    return out
+    return {m.group(1): m.group(2).strip() for m in re.finditer(r"\b(beast_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)}
+
+
+def header_decls():
+    """name -> parameter count, parsed from the prototypes in include/beast_hip.h."""
+    return {name: 0 if args in ("", "void") else args.count(",") + 1 for name, args in header_protos().items()}
 
 
 def test_header_parses():

@@ -12,18 +12,18 @@ FAKE = C.c_void_p(16)                   # never dereferenced: validation fails f
 
 
 def fwd_args(**kw):
-    """logits, dtype, B, K, V, sb, sk, temperature, tok_offset, mean_out, argmax_out, stats_out, hip_stream"""
+    """logits, dtype, B, K, V, sb, sk, temperature, tok_offset, mean_out, argmax_out, stats_out, stream"""
     a = dict(logits=FAKE, dtype=0, B=4, K=140, V=256, sb=140 * 256, sk=256, temperature=1.0, tok_offset=0,
-             mean_out=FAKE, argmax_out=FAKE, stats_out=FAKE, hip_stream=None)
+             mean_out=FAKE, argmax_out=FAKE, stats_out=FAKE, stream=None)
     assert set(kw) <= set(a)
     a.update(kw)
     return list(a.values())
 
 
 def bwd_args(**kw):
-    """logits, dtype, B, K, V, sb, sk, temperature, mean, stats, grad_mean, grad_logits, gsb, gsk, hip_stream"""
+    """logits, dtype, B, K, V, sb, sk, temperature, mean, stats, grad_mean, grad_logits, gsb, gsk, stream"""
     a = dict(logits=FAKE, dtype=2, B=4, K=140, V=256, sb=140 * 256, sk=256, temperature=1.0, mean=FAKE, stats=FAKE,
-             grad_mean=FAKE, grad_logits=FAKE, gsb=140 * 256, gsk=256, hip_stream=None)
+             grad_mean=FAKE, grad_logits=FAKE, gsb=140 * 256, gsk=256, stream=None)
     assert set(kw) <= set(a)
     a.update(kw)
     return list(a.values())

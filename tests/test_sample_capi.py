@@ -15,9 +15,9 @@ NAME = "beast_sample_rows"
 
 def args(**kw):
     """logits, dtype, B, K, V, sb, sk, temperature, top_k, top_p, uniforms, S, tok_offset, tokens_out,
-    logprob_out, kept_out, sample_stream"""
+    logprob_out, kept_out, stream"""
     a = dict(logits=FAKE, dtype=0, B=4, K=140, V=256, sb=140 * 256, sk=256, temperature=1.0, top_k=0, top_p=1.0,
-             uniforms=FAKE, S=1, tok_offset=0, tokens_out=FAKE, logprob_out=FAKE, kept_out=FAKE, sample_stream=None)
+             uniforms=FAKE, S=1, tok_offset=0, tokens_out=FAKE, logprob_out=FAKE, kept_out=FAKE, stream=None)
     assert set(kw) <= set(a)
     a.update(kw)
     return list(a.values())

@@ -19,19 +19,19 @@ def common(**kw):
 
 
 def fwd_args(**kw):
-    """the common inputs, then logprob_out, entropy_out, kl_out, kept_out, stats_out, score_stream"""
+    """the common inputs, then logprob_out, entropy_out, kl_out, kept_out, stats_out, stream"""
     a = common()
-    a.update(logprob_out=FAKE, entropy_out=FAKE, kl_out=FAKE, kept_out=FAKE, stats_out=FAKE, score_stream=None)
+    a.update(logprob_out=FAKE, entropy_out=FAKE, kl_out=FAKE, kept_out=FAKE, stats_out=FAKE, stream=None)
     assert set(kw) <= set(a), kw
     a.update(kw)
     return list(a.values())
 
 
 def bwd_args(**kw):
-    """the common inputs, then stats, grad_logprob, grad_entropy, grad_kl, grad_logits, gsb, gsk, score_stream"""
+    """the common inputs, then stats, grad_logprob, grad_entropy, grad_kl, grad_logits, gsb, gsk, stream"""
     a = common()
     a.update(stats=FAKE, grad_logprob=FAKE, grad_entropy=FAKE, grad_kl=FAKE, grad_logits=FAKE, gsb=140 * 256, gsk=256,
-             score_stream=None)
+             stream=None)
     assert set(kw) <= set(a), kw
     a.update(kw)
     return list(a.values())

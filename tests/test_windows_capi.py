@@ -16,7 +16,7 @@ def win_args(**kw):
     """The argument list of beast_encode_windows_f32, in the header's order."""
     a = dict(frames=FAKE, R=1000, sr=14, sd=1, row_elems=14, win_start=FAKE, win_end=FAKE, W=4, T=50, D=14,
              n_joint=12, dof_src=FAKE, proj=FAKE, N=10, w_min=FAKE, w_max=FAKE, vocab=256, tok_offset=0,
-             params_out=FAKE, tokens_out=FAKE, tile_counts=FAKE, windows_stream=None)
+             params_out=FAKE, tokens_out=FAKE, tile_counts=FAKE, stream=None)
     assert set(kw) <= set(a)
     a.update(kw)
     return list(a.values())

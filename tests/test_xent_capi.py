@@ -14,10 +14,10 @@ FAKE = C.c_void_p(16)                   # never dereferenced: validation fails f
 
 def fwd_args(**kw):
     """logits, dtype, B, K, V, sb, sk, target_tok, target_pos, tok_offset, ignore_index, smoothing, loss_out,
-    stats_out, argmax_out, queue_stream"""
+    stats_out, argmax_out, stream"""
     a = dict(logits=FAKE, dtype=0, B=4, K=140, V=256, sb=140 * 256, sk=256, target_tok=FAKE, target_pos=None,
              tok_offset=0, ignore_index=-100, smoothing=0.0, loss_out=FAKE, stats_out=FAKE, argmax_out=FAKE,
-             queue_stream=None)
+             stream=None)
     assert set(kw) <= set(a)
     a.update(kw)
     return list(a.values())
@@ -25,10 +25,10 @@ def fwd_args(**kw):
 
 def bwd_args(**kw):
     """logits, dtype, B, K, V, sb, sk, target_tok, target_pos, tok_offset, ignore_index, smoothing, stats,
-    grad_loss, grad_logits, gsb, gsk, queue_stream"""
+    grad_loss, grad_logits, gsb, gsk, stream"""
     a = dict(logits=FAKE, dtype=2, B=4, K=140, V=256, sb=140 * 256, sk=256, target_tok=None, target_pos=FAKE,
              tok_offset=0, ignore_index=-100, smoothing=0.1, stats=FAKE, grad_loss=FAKE, grad_logits=FAKE,
-             gsb=140 * 256, gsk=256, queue_stream=None)
+             gsb=140 * 256, gsk=256, stream=None)
     assert set(kw) <= set(a)
     a.update(kw)
     return list(a.values())
