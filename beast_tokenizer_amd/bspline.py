@@ -2,7 +2,7 @@
 
 The reference rebuilds the basis for every call (uni_bspline.py:539, :160); here
 the basis Phi [2][T][N] (kind 0 = joint degree p, kind 1 = gripper degree 0) and
-the ridge projection P [2][16][Tp] (float64, and its fp32 image for the kernel) are evaluated ON THE GPU by
+the ridge projection P [2][Np][Tp] (Np = 16, or 32 for num_basis > 16; float64, and its fp32 image for the kernel) are evaluated ON THE GPU by
 ``beast_bspline_basis_f32`` / ``beast_bspline_projection_f64`` once per time grid
 and cached; the per-batch kernels only read them.
 
@@ -239,18 +239,23 @@ class DeviceBasis:
         proj[0, :, :T] = pe - pe @ d.T
 
     def constants(self, times: torch.Tensor, version: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(Phi [2][T][N] fp32, P [2][16][Tp] fp64 zero-padded, P in fp32) for a 1-D grid,
-        cached per (device, version, T).  The encode kernel reads the fp32 image of P."""
+        """(Phi [2][T][N] fp32, P [2][Np][Tp] fp64 zero-padded, P in fp32) for a 1-D grid,
+        cached per (device, version, T); Np = 16 row-tile rows for N <= 16, 32 for N <= 32.  The
+        encode kernels read the fp32 image of P."""
         key = (times.device, version, times.numel())
         hit = self._cache.get(key)
         if hit is not None:
             return hit
-        self._drop_stale(times.device, version)
         T, N = times.numel(), self.num_basis
+        if self.conditioned and (N > 16 or T > 256):
+            raise NotImplementedError(
+                f"init_cond_order / end_cond_order != 0 are supported for num_basis <= 16 and seq_len <= 256 "
+                f"(num_basis={N}, seq_len={T}): the streamed kernels fit unconditioned splines only")
+        self._drop_stale(times.device, version)
         phi = torch.zeros((2, T, N), dtype=torch.float32, device=times.device)
         phi[: self.n_kinds] = self.basis_at(times.reshape(-1))
-        # zero-padded [2][16][Tp] MFMA A-operand layout (beast_bspline_projection_f64)
-        proj = torch.zeros((2, 16, (T + 3) // 4 * 4), dtype=torch.float64, device=times.device)
+        # zero-padded [2][Np][Tp] MFMA A-operand layout (beast_bspline_projection_f64)
+        proj = torch.zeros((2, 16 if N <= 16 else 32, (T + 3) // 4 * 4), dtype=torch.float64, device=times.device)
         s = _lib.stream_of(times.device)
         for k in range(self.n_kinds):
             _lib.run("beast_bspline_projection_f64", phi[k].data_ptr(), T, N, self.reg, proj[k].data_ptr(), s)

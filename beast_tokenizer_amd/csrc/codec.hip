@@ -19,6 +19,8 @@
 //                        k_reconstruct_v (one wave per trajectory) and k_reconstruct_rows (per-row
 //                        basis and decode-only, VALU)
 //   codec_roundtrip.h    k_roundtrip: encode -> reconstruct error statistics in one launch
+//   codec_stream.h       k_encode_stream / k_reconstruct_wide: N up to 32, T up to 4096, with the time
+//                        axis streamed through LDS in chunks; their plans (tile, chunk length)
 //
 // Which kernel a call gets is decided below (launch_encode, launch_reconstruct, the round-trip
 // dispatch in beast_roundtrip_stats_f32) and reported through BEAST_OPT_LAST_CODEC_LAUNCH.
@@ -35,12 +37,17 @@
 #include "codec_encode.h"
 #include "codec_reconstruct.h"
 #include "codec_roundtrip.h"
+#include "codec_stream.h"
 
 namespace {
 
+// MAX_T / MAX_N: the resident kernels' envelope (and every other entry point's); beast_encode_f32 and
+// beast_reconstruct_f32 go on to STREAM_MAX_T / STREAM_MAX_N through the streamed kernels.
 constexpr int MAX_T = 256;
 constexpr int MAX_N = 16;
 constexpr int MAX_D = 64;
+constexpr int STREAM_MAX_T = 4096;
+constexpr int STREAM_MAX_N = 32;
 
 // Diagnostic / test knob (beast_set_option): run the runtime-shape kernels even where a
 // specialised one exists.
@@ -130,6 +137,25 @@ int launch_encode_t(EncArgs a, int T, int D, int nj, int N, bool fast, const Que
               : launch<k_encode<TBT, false, S>>((unsigned)grid, S::W * 64, L.total, q, "k_encode", a);
 }
 
+// Outside the resident envelope: k_encode_stream, tile and chunk by enc_stream_plan.  Reported as
+// the runtime-shape family with staged = 0: the trajectory is never resident.
+int launch_encode_stream(EncArgs a, int T, int D, int nj, int N, const Queue& q) {
+  const bool contiguous = a.sd == 1 && a.st == a.row_elems && a.sb == (int64_t)T * a.row_elems;
+  const EncStreamPlan p = enc_stream_plan(D, a.row_elems, nj, N, contiguous);
+  a.g = make_geom<1>(D, nj, N, T);
+  a.ntiles = (a.B + p.tbt - 1) / p.tbt;
+  const EsSmem L = es_smem(p.tbt, p.tc, p.fast ? a.row_elems : D, D, N, N <= 16 ? 16 : 32, nj < D ? 2 : 1);
+  BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "streamed encode tile needs %d B of LDS", L.total);
+  const int a16 = p.fast && (((uintptr_t)a.traj) & 15) == 0 && (a.sb & 3) == 0;   // 16-byte DMA units
+  const unsigned grid = (unsigned)grid_for(a.ntiles, L.total, q.dev);
+  mark_launch(launch_mark(FAM_ENCODE_DYN, p.tbt, ST_NW, 0, p.fast, false, false, false));
+  if (N <= 16)
+    return p.fast ? launch<k_encode_stream<1, true>>(grid, ST_NT, L.total, q, "k_encode_stream", a, p.tbt, p.tc, a16)
+                  : launch<k_encode_stream<1, false>>(grid, ST_NT, L.total, q, "k_encode_stream", a, p.tbt, p.tc, a16);
+  return p.fast ? launch<k_encode_stream<2, true>>(grid, ST_NT, L.total, q, "k_encode_stream", a, p.tbt, p.tc, a16)
+                : launch<k_encode_stream<2, false>>(grid, ST_NT, L.total, q, "k_encode_stream", a, p.tbt, p.tc, a16);
+}
+
 int enc_smem_total(int tbt, int T, int Dl, int D, int N, int nkinds) {
   const int Tp = round_up(T, 4);
   switch (tbt) {
@@ -147,6 +173,7 @@ int enc_smem_total(int tbt, int T, int Dl, int D, int N, int nkinds) {
 // The BEAST default shapes (T = 50, N = 10, D = 14 with 0 or 2 gripper DoF, D = 7) run fully
 // specialised kernels.
 int launch_encode(EncArgs a, int T, int D, int nj, int N, const Queue& q) {
+  if (N > MAX_N || T > MAX_T) return launch_encode_stream(a, T, D, nj, N, q);
   const int64_t traj_bytes = (int64_t)T * a.row_elems * 4;
   const bool contiguous = a.sd == 1 && a.st == a.row_elems && a.sb == (int64_t)T * a.row_elems &&
                           (((uintptr_t)a.traj) & 15) == 0 && ((int64_t)T * a.row_elems) % 4 == 0;
@@ -264,6 +291,30 @@ int launch_reconstruct(RecArgs a, int D, int nj, int N, bool shared, const Queue
   return launch_rec_mfma<TBT, 0>(a, D, nj, N, q);
 }
 
+// 17 <= N <= 32 on a shared basis (or decode-only): k_reconstruct_wide, tile and row chunk by
+// rec_wide_plan.  Reported as the runtime-shape MFMA family with ks = 0 (the field cannot hold
+// ceil(N / 4) = 8, and no other MFMA launch reports 0).
+int launch_reconstruct_wide(RecArgs a, int D, int nj, int N, const Queue& q) {
+  // a params_out-only call stages nothing: its plan does not depend on num_dof_out
+  const RecWidePlan p = rec_wide_plan(D, nj, N, a.pos_out ? a.ndo : 0);
+  BEAST_REQUIRE_CODE(p.rc >= 16, BEAST_E_UNSUPPORTED,
+                     "reconstruct with N > 16: 16 output rows of num_dof_out=%d columns do not fit LDS", a.ndo);
+  a.g = make_geom<1>(D, nj, N, 1);
+  a.tbt = p.tbt;
+  a.ntiles = (a.B + p.tbt - 1) / p.tbt;
+  const RwSmem L = rw_smem(p.tbt, p.rc, D, N, a.ndo, nj < D ? 2 : 1, a.pos_out != nullptr);
+  BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "wide reconstruct tile needs %d B of LDS", L.total);
+  const unsigned grid = (unsigned)grid_for(a.ntiles, L.total, q.dev);
+  const float rinv = 1.0f / (float)(a.vocab - 1);   // IEEE division: beast::exact_quotient's r
+  mark_launch(launch_mark(FAM_REC_MFMA, p.tbt, ST_NW, 0, false, false, true, false));
+  switch ((N + 3) / 4) {
+    case 5: return launch<k_reconstruct_wide<5>>(grid, ST_NT, L.total, q, "k_reconstruct_wide", a, p.rc, rinv);
+    case 6: return launch<k_reconstruct_wide<6>>(grid, ST_NT, L.total, q, "k_reconstruct_wide", a, p.rc, rinv);
+    case 7: return launch<k_reconstruct_wide<7>>(grid, ST_NT, L.total, q, "k_reconstruct_wide", a, p.rc, rinv);
+    default: return launch<k_reconstruct_wide<8>>(grid, ST_NT, L.total, q, "k_reconstruct_wide", a, p.rc, rinv);
+  }
+}
+
 template <class S, int WF>
 int launch_roundtrip(const float* traj, int64_t B, RtArgs a, int W, const Queue& q) {
   const RtSmem L = rt_smem(a.T, a.D, a.N, a.nj < a.D ? 2 : 1, W, a.lut_n);
@@ -289,8 +340,9 @@ extern "C" int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb,
                                 float* params_out, int64_t* tokens_out, void* stream) {
   BEAST_REQUIRE(traj && dof_src && proj, "beast_encode_f32: null input pointer");
   BEAST_REQUIRE(params_out || tokens_out, "beast_encode_f32: no output requested");
-  BEAST_REQUIRE(T >= 1 && T <= MAX_T, "seq_len T=%d outside [1, %d]", T, MAX_T);
-  BEAST_REQUIRE(N >= 1 && N <= MAX_N, "num_basis N=%d outside [1, %d]", N, MAX_N);
+  BEAST_REQUIRE(T >= 1 && N >= 1, "beast_encode_f32: seq_len T=%d and num_basis N=%d must be >= 1", T, N);
+  BEAST_REQUIRE_CODE(T <= STREAM_MAX_T && N <= STREAM_MAX_N, BEAST_E_UNSUPPORTED,
+                     "beast_encode_f32 supports T <= %d, N <= %d (T=%d N=%d)", STREAM_MAX_T, STREAM_MAX_N, T, N);
   BEAST_REQUIRE(D >= 1 && D <= MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
   BEAST_REQUIRE(row_elems >= 1, "row_elems must be >= 1");
   BEAST_REQUIRE(!tokens_out || (w_min && w_max && vocab >= 2), "quantisation needs w_min/w_max and vocab >= 2");
@@ -335,7 +387,12 @@ extern "C" int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, in
                                      const float* ntokens, void* stream) {
   BEAST_REQUIRE((tokens || ntokens) && w_min && w_max, "beast_reconstruct_f32: null input pointer");
   BEAST_REQUIRE(params_out || pos_out, "beast_reconstruct_f32: no output requested");
-  BEAST_REQUIRE(N >= 1 && N <= MAX_N, "num_basis N=%d outside [1, %d]", N, MAX_N);
+  BEAST_REQUIRE(N >= 1, "num_basis N=%d must be >= 1", N);
+  BEAST_REQUIRE_CODE(N <= STREAM_MAX_N, BEAST_E_UNSUPPORTED, "beast_reconstruct_f32 supports N <= %d (N=%d)",
+                     STREAM_MAX_N, N);
+  BEAST_REQUIRE_CODE(N <= MAX_N || basis_sb == 0 || !pos_out, BEAST_E_UNSUPPORTED,
+                     "beast_reconstruct_f32: per-trajectory bases stop at N = %d (N=%d): N up to %d needs a shared "
+                     "basis (basis_sb = 0)", MAX_N, N, STREAM_MAX_N);
   BEAST_REQUIRE(D >= 1 && D <= MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
   BEAST_REQUIRE(vocab >= 2 || ntokens, "vocab must be >= 2");
   BEAST_REQUIRE(!pos_out || (basis && dof_dst && T_out >= 1 && T_out <= 4096 && num_dof_out >= D &&
@@ -352,6 +409,7 @@ extern "C" int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, in
   const bool shared = (basis_sb == 0);
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_reconstruct_f32")) return rc;
+  if (N > MAX_N) return launch_reconstruct_wide(a, D, n_joint, N, q);
   return launch_reconstruct<8>(a, D, n_joint, N, shared, q);
 }
 
@@ -394,6 +452,20 @@ extern "C" int beast_roundtrip_stats_f32(const float* traj, int64_t B, int T, in
   while (W > 1 && rt_smem(T, D, N, nkinds, W, a.lut_n).total > 160 * 1024) W >>= 1;
   if (rt_smem(T, D, N, nkinds, W, a.lut_n).total > 160 * 1024) a.lut_n = 0;
   return launch_roundtrip<DynShape, 0>(traj, B, a, W, q);
+}
+
+extern "C" int beast_encode_stream_chunk(int T, int D, int row_elems, int n_joint, int N, int contiguous) {
+  if (T < 1 || T > STREAM_MAX_T || N < 1 || N > STREAM_MAX_N || D < 1 || D > MAX_D || n_joint < 0 || n_joint > D ||
+      row_elems < 1 || (N <= MAX_N && T <= MAX_T))
+    return 0;
+  return enc_stream_plan(D, row_elems, n_joint, N, contiguous != 0).tc;
+}
+
+extern "C" int beast_reconstruct_stream_rows(int T_out, int D, int n_joint, int N, int num_dof_out) {
+  if (T_out < 1 || T_out > 4096 || N <= MAX_N || N > STREAM_MAX_N || D < 1 || D > MAX_D || n_joint < 0 ||
+      n_joint > D || num_dof_out < D || num_dof_out > 4096)
+    return 0;
+  return rec_wide_plan(D, n_joint, N, num_dof_out).rc;
 }
 
 #ifdef BEAST_STAMPS

@@ -5,7 +5,8 @@
 //          k_basis_deriv  its first / second time derivative over the same control points
 //                         (replaces vel_basis + velocity_control_points, :115-190)
 //          k_projection   P = (Phi^T Phi + reg I)^-1 Phi^T in fp64 (one workgroup),
-//                         written zero-padded as [16][Tp] for the encode kernel
+//                         written zero-padded as [Np][Tp] (Np = 16, or 32 for N > 16) for the
+//                         encode kernels
 //   H5     k_quantize     quantise-only epilogue (encode(update_bounds=True), continuous)
 //   H13    k_colminmax_*  column min/max (update_weights_bounds*)
 // The fused encode / reconstruct kernels live in codec.hip.
@@ -109,9 +110,10 @@ __global__ void k_projection(const float* __restrict__ basis, int T, int N, doub
     }
     __syncthreads();
   }
-  // zero-padded [16][Tp] layout consumed directly by k_encode's MFMA A operand
-  const int Tp = (T + 3) & ~3;
-  for (int idx = tid; idx < 16 * Tp; idx += blockDim.x) {
+  // zero-padded [Np][Tp] layout consumed directly by the encode kernels' MFMA A operand: one row
+  // tile of 16 for N <= 16, two for N <= 32
+  const int Tp = (T + 3) & ~3, Np = N <= 16 ? 16 : 32;
+  for (int idx = tid; idx < Np * Tp; idx += blockDim.x) {
     const int n = idx / Tp, t = idx % Tp;
     double s = 0.0;
     if (n < N && t < T)
@@ -242,7 +244,7 @@ extern "C" int beast_bspline_basis_deriv_f32(const float* times, int64_t n_times
 extern "C" int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, double* proj_out,
                                             void* stream) {
   BEAST_REQUIRE(basis && proj_out, "beast_bspline_projection_f64: null pointer");
-  BEAST_REQUIRE(N >= 1 && N <= 16 && T >= 1, "projection: need 1 <= N <= 16, T >= 1 (N=%d T=%d)", N, T);
+  BEAST_REQUIRE(N >= 1 && N <= 32 && T >= 1, "projection: need 1 <= N <= 32, T >= 1 (N=%d T=%d)", N, T);
   Queue q;
   BEAST_TRY(queue_of(stream, q, "beast_bspline_projection_f64"));
   return launch<k_projection>(1, 256, 0, q, "k_projection", basis, T, N, reg, proj_out);

@@ -41,10 +41,12 @@ extern "C" {
 #define BEAST_E_UNSUPPORTED (-3) /* shape outside the kernels' envelope       */
 #define BEAST_E_WORKSPACE (-4)   /* workspace too small                       */
 
-#define BEAST_ABI_VERSION 6   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
+#define BEAST_ABI_VERSION 7   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
                                  4: beast_score_rows, beast_score_rows_bwd; 5: beast_encode_windows_f32;
                                  6: beast_reconstruct_windows_f32, beast_blend_candidates_host,
-                                    beast_blend_member_host */
+                                    beast_blend_member_host;
+                                 7: beast_encode_stream_chunk, beast_reconstruct_stream_rows, the
+                                    [Np][Tp] projection layout and N <= 32 / T <= 4096 */
 
 int beast_abi_version(void);
 const char* beast_last_error(void);
@@ -77,6 +79,10 @@ const char* beast_last_error(void);
  *   bit 18      reconstruct basis operands in registers (0: in LDS, or read per row from memory)
  *   bit 19      output staged through LDS (0 only for k_reconstruct_rows' direct stores)
  *   bit 20      latency variant (write-through stores, one tile per CU) rather than the bulk one
+ * The streamed kernels report through the same families: k_encode_stream as family 3 with bit 19
+ * clear (the trajectory is never resident; every resident encode sets it), k_reconstruct_wide as
+ * family 6 with KS = 0 (ceil(N / 4) reaches 8, past the field; every other family-6 launch has
+ * KS >= 1).  Tile and waves are the kernel's own.
  * BEAST_OPT_LAST_LAUNCH_GRID (tests; read-only): gridDim.x of the last kernel this process launched
  * through the library, whichever entry point started it; 0 before any launch.  A test reads it
  * right after a call to prove that the persistent kernel it means to check walked several tiles.
@@ -125,8 +131,9 @@ int beast_bspline_basis_deriv_f32(const float* times, int64_t n_times, float tau
  * of UniformBSpline.learn_mp_params_from_trajs (mp/uni_bspline.py:539-586) for
  * init/end condition order 0, where the block-diagonal system of
  * basis_multi_dofs (basis_gn/uni_bspline_basis.py:349-356) decouples per DoF.
- * Written zero-padded as proj_out[16][Tp], Tp = round_up(T, 4) (the MFMA A-operand
- * layout of beast_encode_f32).  One workgroup; N <= 16. */
+ * Written zero-padded as proj_out[Np][Tp], Tp = round_up(T, 4), Np = 16 for N <= 16 and 32 for
+ * 17 <= N <= 32 (the MFMA A-operand layout of beast_encode_f32: one or two row tiles); rows
+ * n >= N and columns t >= T are zero.  One workgroup; 1 <= N <= 32, else BEAST_E_INVALID. */
 int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, double* proj_out,
                                  void* stream);
 
@@ -136,14 +143,27 @@ int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, d
  * (beast/utils.py:4-17) + rearrange + LLM offset, as ONE fused kernel.
  *   traj[b*sb + t*st + dof_src[d]*sd]  fp32 input, element strides
  *   row_elems   size of the input's last dim (for the contiguous fast path)
- *   proj        [2][16][Tp] fp32 zero-padded projections (kind 0 joint, kind 1
- *               gripper): the round-to-nearest fp32 image of the float64 output of
- *               beast_bspline_projection_f64, converted once per time grid
+ *   proj        [2][Np][Tp] fp32 zero-padded projections (kind 0 joint, kind 1
+ *               gripper; Np = 16 for N <= 16, 32 above): the round-to-nearest fp32 image of the
+ *               float64 output of beast_bspline_projection_f64, converted once per time grid
  *   params_out  [B][D*N] fp32 unclamped fit (params_dict['params']); nullable
  *   tokens_out  [B][N*D] int64 = round_half_even(clamp01((clamp(p)-wmin)/max(wmax-wmin,1e-8))*(vocab-1))
  *               + tok_offset; nullable.  vocab <= 0 disables quantisation.
- * Constraints: N <= 16, T <= 256, D <= 64; every shape inside them encodes, at any strides and
- * alignment (16-byte aligned contiguous rows of at most 32 KB per trajectory take the DMA path). */
+ * Constraints: N <= 32, T <= 4096, D <= 64 (BEAST_E_UNSUPPORTED above; N < 1 or T < 1 is
+ * BEAST_E_INVALID); every shape inside them encodes, at any strides and alignment.  Two envelopes:
+ *   N <= 16 and T <= 256   the resident kernels: a tile's trajectories and the whole projection sit
+ *                          in LDS (16-byte aligned contiguous rows of at most 32 KB per trajectory
+ *                          take the DMA path);
+ *   beyond either          k_encode_stream: both operands move through LDS in chunks of
+ *                          beast_encode_stream_chunk() time steps, double-buffered (contiguous rows by
+ *                          LDS-DMA, other layouts gathered).  Nothing past a trajectory's last sample
+ *                          is read.  An output's summation order depends on (T, chunk) alone, so a
+ *                          trajectory's params and tokens are the same bits alone or in any batch.
+ * A dof_src entry outside [0, row_elems) is caller error: rows read in place by DMA clamp it into
+ * the row, gathered rows read it as 0.0 (on both envelopes), so the result then depends on the layout.
+ * proj must be 16-byte aligned (its rows are fetched in 16-byte units; Tp is a multiple of 4).
+ * On both, tokens_out is bitwise beast_quantize_f32 (mode 0) of params_out.  Every other entry point
+ * that fits (beast_encode_list_f32, _rows, _windows, beast_roundtrip_stats_f32) keeps N <= 16, T <= 256. */
 int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st, int64_t sd, int row_elems,
                      int D, int n_joint, const int32_t* dof_src, const float* proj, int N,
                      const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
@@ -303,13 +323,31 @@ int beast_blend_member_host(int64_t start, int64_t end, int64_t R, int T, int64_
  *   params_out  nullable [B][D*N] decoded params (= decode()); pos_out nullable.
  *   ntokens     nullable: when set, fp32 normalised tokens [B][N*D] in [-1, 1] are
  *               read instead of `tokens` and mapped back by denormalize_tensor
- *               (beast/utils.py:38-44): the reconstruct_traj_continuous path (:538-582). */
+ *               (beast/utils.py:38-44): the reconstruct_traj_continuous path (:538-582).
+ * N <= 16: any basis (shared or per trajectory), the resident kernels.  17 <= N <= 32: a shared
+ * basis only (basis_sb == 0, or a params_out-only call), T_out <= 4096, by k_reconstruct_wide: the
+ * basis moves through LDS in chunks of beast_reconstruct_stream_rows() output rows, staged there and
+ * stored per chunk (16 rows of num_dof_out columns must fit LDS, num_dof_out <= 640 at worst, else BEAST_E_UNSUPPORTED).
+ * BEAST_E_UNSUPPORTED: N > 32; N > 16 with basis_sb != 0 (per-trajectory bases stop at N = 16). */
 int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, int n_joint, int N, int vocab,
                           int64_t tok_offset, const float* w_min, const float* w_max,
                           const float* basis, int64_t basis_sb, int T_out,
                           const int32_t* dof_dst, int num_dof_out,
                           const float* init_p, int64_t init_p_sb, const int32_t* init_p_src,
                           float* params_out, float* pos_out, const float* ntokens, void* stream);
+
+/* Host only, no launch: the chunk lengths the two entry points above stream with (the dispatch
+ * calls the same functions), so a caller or a test can place a shape on a chunk boundary.
+ * beast_encode_stream_chunk: time steps per chunk of beast_encode_f32 for this shape, a positive
+ * multiple of 4; `contiguous` != 0: unit element stride, rows of row_elems floats, trajectories of
+ * T rows back to back (sd == 1, st == row_elems, sb == T * row_elems).  It depends on T only
+ * through the envelope: 0 where a resident kernel serves the shape (N <= 16 and T <= 256) and for
+ * arguments beast_encode_f32 rejects.
+ * beast_reconstruct_stream_rows: output rows per chunk of beast_reconstruct_f32 on a shared basis, a
+ * positive multiple of 16 that does not depend on T_out; 0 for N <= 16, for arguments
+ * beast_reconstruct_f32 rejects and where 16 rows of num_dof_out columns do not fit LDS. */
+int beast_encode_stream_chunk(int T, int D, int row_elems, int n_joint, int N, int contiguous);
+int beast_reconstruct_stream_rows(int T_out, int D, int n_joint, int N, int num_dof_out);
 
 /* Positions, velocities and accelerations from tokens in ONE launch: what
  * UniformBSpline.get_traj_pos / get_traj_vel / get_traj_acc (mp/uni_bspline.py:114-177,
