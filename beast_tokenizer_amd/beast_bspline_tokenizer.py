@@ -889,15 +889,16 @@ class BEASTBsplineTokenizer(TokenizerBase):
 
     def _listable(self, x, group) -> bool:
         """Can batch ``x`` join ``group`` for one beast_encode_list_f32 launch?  Device-resident
-        contiguous fp32 [B, T, D] with B % 8 == 0 and 16-byte aligned rows, all of one shape
-        (anything else takes the per-batch path, as does every shape outside the list entry's
-        envelope, num_basis <= 16 and seq_len <= 256)."""
-        if not isinstance(x, torch.Tensor) or self._conditioned or x.dim() != 3 or self.num_basis > 16:
+        contiguous fp32 [B, T, D] with B % 8 == 0, all of one shape; inside num_basis <= 16 and
+        seq_len <= 256 (the resident kernel) also 16-byte aligned whole-vector rows, which the
+        streamed kernel beyond does not need.  Anything else takes the per-batch path."""
+        if not isinstance(x, torch.Tensor) or self._conditioned or x.dim() != 3:
             return False
         p = self._plan()
-        if (p.T > 256 or x.device != p.dev or x.dtype is not torch.float32 or not x.is_contiguous() or x.shape[0] == 0
-                or x.shape[0] % 8 or x.shape[1] != p.T or x.shape[2] < p.min_din or x.data_ptr() % 16
-                or (x.shape[1] * x.shape[2]) % 4):
+        streamed = self.num_basis > 16 or p.T > 256
+        if (x.device != p.dev or x.dtype is not torch.float32 or not x.is_contiguous() or x.shape[0] == 0
+                or x.shape[0] % 8 or x.shape[1] != p.T or x.shape[2] < p.min_din
+                or (not streamed and (x.data_ptr() % 16 or (x.shape[1] * x.shape[2]) % 4))):
             return False
         return not group or group[0].shape == x.shape
 

@@ -19,8 +19,9 @@
 //                        k_reconstruct_v (one wave per trajectory) and k_reconstruct_rows (per-row
 //                        basis and decode-only, VALU)
 //   codec_roundtrip.h    k_roundtrip: encode -> reconstruct error statistics in one launch
-//   codec_stream.h       k_encode_stream / k_reconstruct_wide: N up to 32, T up to 4096, with the time
-//                        axis streamed through LDS in chunks; their plans (tile, chunk length)
+//   codec_stream.h       k_encode_stream / k_encode_stream_list / k_reconstruct_wide: N up to 32, T up
+//                        to 4096, with the time axis streamed through LDS in chunks; their plans
+//                        (tile, chunk length)
 //
 // Which kernel a call gets is decided below (launch_encode, launch_reconstruct, the round-trip
 // dispatch in beast_roundtrip_stats_f32) and reported through BEAST_OPT_LAST_CODEC_LAUNCH.
@@ -41,8 +42,9 @@
 
 namespace {
 
-// MAX_T / MAX_N: the resident kernels' envelope (and every other entry point's); beast_encode_f32 and
-// beast_reconstruct_f32 go on to STREAM_MAX_T / STREAM_MAX_N through the streamed kernels.
+// MAX_T / MAX_N: the resident kernels' envelope (and every other entry point's); beast_encode_f32,
+// beast_encode_list_f32 and beast_reconstruct_f32 go on to STREAM_MAX_T / STREAM_MAX_N through the
+// streamed kernels.
 constexpr int MAX_T = 256;
 constexpr int MAX_N = 16;
 constexpr int MAX_D = 64;
@@ -154,6 +156,27 @@ int launch_encode_stream(EncArgs a, int T, int D, int nj, int N, const Queue& q)
                   : launch<k_encode_stream<1, false>>(grid, ST_NT, L.total, q, "k_encode_stream", a, p.tbt, p.tc, a16);
   return p.fast ? launch<k_encode_stream<2, true>>(grid, ST_NT, L.total, q, "k_encode_stream", a, p.tbt, p.tc, a16)
                 : launch<k_encode_stream<2, false>>(grid, ST_NT, L.total, q, "k_encode_stream", a, p.tbt, p.tc, a16);
+}
+
+// beast_encode_list_f32 outside the resident envelope: k_encode_stream_list on enc_stream_plan's tile
+// and chunk (the plan of beast_encode_f32 on the same contiguous rows, so the same bits), the same
+// mark.  Every tile is full: rows_per_batch is a multiple of 8, the tile divides 8.  The table is
+// device memory, so only sb's half of the 16-byte DMA condition is known here; the kernel checks
+// each tile's table entry.
+int launch_encode_stream_list(EncArgs a, int T, int D, int nj, int N, const Queue& q) {
+  const EncStreamPlan p = enc_stream_plan(D, a.row_elems, nj, N, true);
+  a.g = make_geom<1>(D, nj, N, T);
+  a.ntiles = a.B / p.tbt;
+  const ElSmem L = el_smem(p.tbt, p.tc, p.fast ? a.row_elems : D, N <= 16 ? 16 : 32, nj < D ? 2 : 1);
+  BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "streamed encode tile needs %d B of LDS", L.total);
+  const int a16 = p.fast && (a.sb & 3) == 0;
+  const unsigned grid = (unsigned)grid_for(a.ntiles, L.total, q.dev);
+  mark_launch(launch_mark(FAM_ENCODE_DYN, p.tbt, ST_NW, 0, p.fast, false, false, false));
+  if (N <= 16)
+    return p.fast ? launch<k_encode_stream_list<1, true>>(grid, ST_NT, L.total, q, "k_encode_stream_list", a, p.tbt, p.tc, a16)
+                  : launch<k_encode_stream_list<1, false>>(grid, ST_NT, L.total, q, "k_encode_stream_list", a, p.tbt, p.tc, a16);
+  return p.fast ? launch<k_encode_stream_list<2, true>>(grid, ST_NT, L.total, q, "k_encode_stream_list", a, p.tbt, p.tc, a16)
+                : launch<k_encode_stream_list<2, false>>(grid, ST_NT, L.total, q, "k_encode_stream_list", a, p.tbt, p.tc, a16);
 }
 
 int enc_smem_total(int tbt, int T, int Dl, int D, int N, int nkinds) {
@@ -363,10 +386,11 @@ extern "C" int beast_encode_list_f32(const float* const* traj_list, int nbatch, 
   BEAST_REQUIRE(traj_list && dof_src && proj && params_out, "beast_encode_list_f32: null pointer");
   BEAST_REQUIRE(nbatch >= 0 && rows_per_batch >= 0, "beast_encode_list_f32: negative sizes");
   BEAST_REQUIRE(rows_per_batch % 8 == 0, "rows_per_batch=%lld is not a multiple of 8", (long long)rows_per_batch);
-  BEAST_REQUIRE(T >= 1 && T <= MAX_T, "seq_len T=%d outside [1, %d]", T, MAX_T);
-  BEAST_REQUIRE(N >= 1 && N <= MAX_N, "num_basis N=%d outside [1, %d]", N, MAX_N);
+  BEAST_REQUIRE(T >= 1 && T <= STREAM_MAX_T, "seq_len T=%d outside [1, %d]", T, STREAM_MAX_T);
+  BEAST_REQUIRE(N >= 1 && N <= STREAM_MAX_N, "num_basis N=%d outside [1, %d]", N, STREAM_MAX_N);
   BEAST_REQUIRE(D >= 1 && D <= MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
-  BEAST_REQUIRE(row_elems >= 1 && ((int64_t)T * row_elems) % 4 == 0,
+  const bool streamed = N > MAX_N || T > MAX_T;   // k_encode_stream_list: any row length, 4-byte DMA units if need be
+  BEAST_REQUIRE(row_elems >= 1 && (streamed || ((int64_t)T * row_elems) % 4 == 0),
                 "beast_encode_list_f32: T*row_elems must be a multiple of 4");
   if (nbatch == 0 || rows_per_batch == 0) return BEAST_OK;
   EncArgs a{};
@@ -376,6 +400,7 @@ extern "C" int beast_encode_list_f32(const float* const* traj_list, int nbatch, 
   a.params_out = params_out;
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_encode_list_f32")) return rc;
+  if (streamed) return launch_encode_stream_list(a, T, D, n_joint, N, q);
   return launch_encode(a, T, D, n_joint, N, q);
 }
 

@@ -1,5 +1,5 @@
-// Time-streamed codec kernels (codec.hip's fifth layer): k_encode_stream and k_reconstruct_wide,
-// for the shapes whose time axis or basis does not fit the resident kernels (17 <= N <= 32, or
+// Time-streamed codec kernels (codec.hip's fifth layer): k_encode_stream, its list-source form
+// k_encode_stream_list (beast_encode_list_f32, params only) and k_reconstruct_wide, for the shapes whose time axis or basis does not fit the resident kernels (17 <= N <= 32, or
 // 257 <= T <= 4096 on encode).  Neither keeps a trajectory, the projection or the basis resident:
 // both operands of the fit, and the basis and the output of the reconstruction, move through LDS in
 // chunks of the time axis, the next chunk in flight while the current one is multiplied.  The plans
@@ -280,6 +280,209 @@ __global__ BEAST_NO_PK_F32 __launch_bounds__(ST_NT) void k_encode_stream(EncArgs
         }
     st_sync();
     enc_store_tile<S>(a, m, pb, kq, wlo, whi, b0, nb, vm1, false);
+  }
+}
+
+// ----------------------------------------------------------- encode, list --
+// Wave-instruction rounds (ST_NT lanes x 16 bytes) a chunk of y / of P takes at most: enc_stream_plan
+// keeps one buffer of both within ST_BYTES / 2, and P's is at most 2 kinds x 32 rows x ST_MAX_TC steps.
+constexpr int SL_YIT = ST_BYTES / 2 / (ST_NT * 16);
+constexpr int SL_PIT = 2 * 32 * ST_MAX_TC * 4 / (ST_NT * 16);
+
+struct ElSmem {
+  int Y, ybuf, P, pbuf, total;   // Y / P: buffer 0; buffer 1 lies ybuf / pbuf bytes on
+};
+__host__ __device__ __forceinline__ ElSmem el_smem(int tbt, int tc, int Dl, int Np, int nkinds) {
+  ElSmem s;
+  s.ybuf = round_up(tbt * tc * Dl * 4, 1024);   // DMA destinations: whole wave-instructions
+  s.pbuf = round_up(nkinds * Np * tc * 4, 1024);
+  s.Y = 0;
+  s.P = 2 * s.ybuf;
+  s.total = 2 * s.ybuf + 2 * s.pbuf;
+  return s;
+}
+
+// k_encode_stream's fit for beast_encode_list_f32: the same products in the same order (so the same
+// bits for the same (T, TC)), params only, the rows of tile b0 taken from the pointer table
+// (batch = b0 / list_rows; list_rows is a multiple of 8 and the tile divides 8, so every tile is
+// full and lies in one batch).  What differs from k_encode_stream:
+//   One chunk sequence for the whole workgroup.  Chunks are numbered through the tiles a persistent
+//   workgroup walks (buffer = running count & 1, not the chunk's index in its tile), and the barrier
+//   that opens a tile's last chunk is followed by the DMA of the NEXT tile's first chunk: two chunks
+//   are in flight across the tile change as inside a tile.  The next tile's table entry is loaded
+//   once, at the head of the current tile, a whole tile ahead of its first use.
+//   Lane addresses.  Every tile being full, the segment and unit a lane fetches in round `it` of a
+//   chunk's DMA are the same for every chunk of every tile: their offsets (yo: segment * sb + unit;
+//   po / pu for P, whose last chunk clamps the unit) are divided out once per workgroup, and a DMA
+//   round is one 64-bit add to the tile's base.  16-byte units where sb % 4 == 0 (a16, the host's)
+//   and the tile's table entry is 16-byte aligned -- that half is decided per tile, wave-uniformly,
+//   on the device: the table is device memory the host cannot read in stream order -- else 4-byte
+//   units (dma_segments<1>).  FAST false (rows too long for eight steps of them): gathered DoF by
+//   DoF from the table's rows; so is the last, partial chunk, zeros stored for t >= T.
+//   No epilogue in LDS.  There are no bounds, no quantiser and no token image, so there is no params
+//   image either: a lane's four accumulator rows are four consecutive n of one (trajectory, DoF),
+//   stored from registers (16 bytes where N % 4 == 0 and params_out is aligned).  LDS is the two
+//   chunk buffers alone and a tile ends without a barrier.
+template <int NRT, bool FAST>
+__global__ BEAST_NO_PK_F32 __launch_bounds__(ST_NT) void k_encode_stream_list(EncArgs a, int tbt, int TC, int a16) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  using S = DynShape;
+  constexpr int Np = 16 * NRT;
+  const Dims<S> m(a.g);
+  const int D = m.D, N = m.N, T = m.T, Tp = m.Tp, DN = D * N, nj = m.nj, ng = m.ng;
+  const int Dl = FAST ? a.row_elems : D;
+  const int nkinds = (nj < D) ? 2 : 1;
+  const ElSmem L = el_smem(tbt, TC, Dl, Np, nkinds);
+  const int tid = threadIdx.x, wb = tid & ~63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int lr = lane & 15, lk = lane >> 4;
+  if ((int64_t)blockIdx.x >= a.ntiles) return;
+  // this wave's column tiles: trajectory, DoF, kind and input column of the lane's MFMA column
+  const int nq = st_coltiles(tbt, D, nj);
+  int cj[ST_CT], cd[ST_CT], ck[ST_CT], cc[ST_CT];
+  bool cok[ST_CT], act[ST_CT];
+#pragma unroll
+  for (int i = 0; i < ST_CT; ++i) {
+    const int q = wave + ST_NW * i;
+    act[i] = q < nq;   // wave-uniform
+    st_tile_col(tbt, nj, ng, min(q, nq - 1), lr, cj[i], cd[i], ck[i], cok[i]);
+    cok[i] = cok[i] && act[i];
+    cc[i] = FAST ? min(max(a.dof_src[cd[i]], 0), Dl - 1) : cd[i];
+  }
+  const int nch = (T + TC - 1) / TC;
+  // the lane's DMA offsets (floats): round `it` fetches unit it * ST_NT + tid of the chunk
+  const int pups = TC >> 2, pn = nkinds * Np * pups;        // P: segments of TC / 4 units, Tp apart
+  const int yups = (TC * Dl) >> 2, yn = tbt * yups;         // y: segments of TC * Dl / 4 units, sb apart
+  int po[SL_PIT], pu[SL_PIT];
+  int64_t yo[SL_YIT];
+#pragma unroll
+  for (int it = 0; it < SL_PIT; ++it) {
+    const int i = min(it * ST_NT + tid, pn - 1), s = i / pups;
+    po[it] = s * Tp;
+    pu[it] = i - s * pups;
+  }
+#pragma unroll
+  for (int it = 0; it < SL_YIT; ++it) {
+    const int i = min(it * ST_NT + tid, yn - 1), s = i / yups;
+    yo[it] = FAST ? s * a.sb + (int64_t)(i - s * yups) * 4 : 0;
+  }
+  const float* const* list = a.traj_list;
+  const int64_t list_rows = a.list_rows;
+  // first row of tile `tile`: one table entry, wave-uniform
+  auto tile_src = [&](int64_t tile) ST_INLINE {
+    const int64_t b0 = tile * tbt;
+    const uint64_t bi = (uint64_t)b0 / (uint64_t)list_rows;
+    return list[bi] + (b0 - (int64_t)bi * list_rows) * a.sb;
+  };
+  // chunk c of the tile whose rows start at src, both operands -> buffer buf
+  auto load_chunk = [&](const float* src, int c, int buf) ST_INLINE {
+    const int t0 = c * TC, tc = min(TC, T - t0);
+    float* Pb = reinterpret_cast<float*>(smem + L.P + buf * L.pbuf);
+    float* Yb = reinterpret_cast<float*>(smem + L.Y + buf * L.ybuf);
+    const int plast = (min(TC, Tp - t0) >> 2) - 1;   // the last whole unit of P's rows from t0 on
+#pragma unroll
+    for (int it = 0; it < SL_PIT; ++it)
+      if (it * ST_NT + wb < pn)
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(a.proj + t0 + po[it] + min(pu[it], plast) * 4),
+                                         (lds_void*)(reinterpret_cast<uint4*>(Pb) + it * ST_NT + wb), 16, 0, 0);
+    if (FAST && tc == TC) {
+      const float* y0 = src + (int64_t)t0 * Dl;
+      if (a16 && (((uintptr_t)src) & 15) == 0) {
+#pragma unroll
+        for (int it = 0; it < SL_YIT; ++it)
+          if (it * ST_NT + wb < yn)
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(y0 + yo[it]),
+                                             (lds_void*)(reinterpret_cast<uint4*>(Yb) + it * ST_NT + wb), 16, 0, 0);
+      } else {
+        dma_segments<1>(Yb, y0, tbt, TC * Dl, a.sb, TC * Dl);
+      }
+    } else {
+      const int rows = round_up(tc, 4), pt = rows * Dl;
+      for (int e = tid; e < tbt * pt; e += ST_NT) {
+        const int j = e / pt, r = e - j * pt, t = r / Dl, d = r - t * Dl;
+        const int col = FAST ? d : a.dof_src[d];
+        const bool in = t < tc && col >= 0 && col < a.row_elems;
+        Yb[(j * TC + t) * Dl + d] = in ? src[j * a.sb + (int64_t)(t0 + t) * a.row_elems + col] : 0.0f;
+      }
+    }
+  };
+
+  int64_t tile = blockIdx.x;
+  const float* src = tile_src(tile);
+  int gc = 0;   // chunks this workgroup has opened: chunk gc lies in buffer gc & 1
+  load_chunk(src, 0, 0);
+  for (;;) {
+    const int64_t next = tile + gridDim.x;
+    const float* nsrc = next < a.ntiles ? tile_src(next) : nullptr;
+    float4_t acc[ST_CT][NRT][2];
+#pragma unroll
+    for (int i = 0; i < ST_CT; ++i)
+#pragma unroll
+      for (int rt = 0; rt < NRT; ++rt) acc[i][rt][0] = acc[i][rt][1] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
+
+    for (int c = 0; c < nch; ++c, ++gc) {
+      // Chunk gc has landed (DMA: vmcnt; gather: LDS stores); chunk gc - 1 is consumed.  The wait for
+      // this wave's own DMA is spelled out: the workgroup-scope release fence of st_sync leaves it to
+      // the compiler's wait-count pass, which in this loop -- entered with nothing outstanding, the
+      // DMA issued at its bottom -- put no vmcnt wait in front of the barrier (seen in the ISA, and as
+      // other waves' stale rows under load).
+      __builtin_amdgcn_s_waitcnt(0);
+      st_sync();
+      const bool more = c + 1 < nch;   // else the next tile's first chunk, ahead of this tile's stores
+      if (more || nsrc != nullptr) load_chunk(more ? src : nsrc, more ? c + 1 : 0, (gc + 1) & 1);
+      const float* Pb = reinterpret_cast<const float*>(smem + L.P + (gc & 1) * L.pbuf);
+      const float* Yb = reinterpret_cast<const float*>(smem + L.Y + (gc & 1) * L.ybuf);
+      const int nst = (min(TC, T - c * TC) + 3) >> 2;
+      // K-step s covers t = 4 s + lane / 16 of the chunk; steps in pairs, even -> chain 0, odd -> chain 1
+      for (int s = 0; s < nst; s += 2) {
+        const bool two = s + 1 < nst;   // wave-uniform
+        const int r0 = 4 * s + lk, r1 = two ? r0 + 4 : r0;
+#pragma unroll
+        for (int i = 0; i < ST_CT; ++i) {
+          if (!act[i]) continue;
+          const float* yc = Yb + cj[i] * TC * Dl + cc[i];
+          const float y0 = yc[r0 * Dl], y1 = yc[r1 * Dl];
+          float x0[NRT], x1[NRT];
+#pragma unroll
+          for (int rt = 0; rt < NRT; ++rt) {
+            const float* pa = Pb + (ck[i] * Np + rt * 16 + lr) * TC;
+            x0[rt] = pa[r0];
+            x1[rt] = pa[r1];
+          }
+#pragma unroll
+          for (int rt = 0; rt < NRT; ++rt) {
+            acc[i][rt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[rt], y0, acc[i][rt][0], 0, 0, 0);
+            if (two) acc[i][rt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[rt], y1, acc[i][rt][1], 0, 0, 0);
+          }
+        }
+      }
+    }
+    // f32 C/D map: column = lane & 15, rows n = 16 rt + 4 (lane >> 4) + r, r = 0 .. 3: four consecutive
+    // floats of params[b0 + j][d][.]; the two chains meet once
+    if (a.phases & 4) {
+      float* out = a.params_out + tile * tbt * DN;
+      const bool v4 = (N & 3) == 0 && (((uintptr_t)a.params_out) & 15) == 0;   // wave-uniform
+#pragma unroll
+      for (int i = 0; i < ST_CT; ++i)
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) {
+          const int n0 = rt * 16 + lk * 4;
+          if (!cok[i] || n0 >= N) continue;
+          float4_t v;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = __fadd_rn(acc[i][rt][0][r], acc[i][rt][1][r]);
+          float* q = out + cj[i] * DN + cd[i] * N + n0;
+          if (v4) {
+            *reinterpret_cast<float4_t*>(q) = v;
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (n0 + r < N) q[r] = v[r];
+          }
+        }
+    }
+    if (nsrc == nullptr) break;
+    tile = next;
+    src = nsrc;
   }
 }
 

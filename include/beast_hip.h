@@ -162,8 +162,9 @@ int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, d
  * A dof_src entry outside [0, row_elems) is caller error: rows read in place by DMA clamp it into
  * the row, gathered rows read it as 0.0 (on both envelopes), so the result then depends on the layout.
  * proj must be 16-byte aligned (its rows are fetched in 16-byte units; Tp is a multiple of 4).
- * On both, tokens_out is bitwise beast_quantize_f32 (mode 0) of params_out.  Every other entry point
- * that fits (beast_encode_list_f32, _rows, _windows, beast_roundtrip_stats_f32) keeps N <= 16, T <= 256. */
+ * On both, tokens_out is bitwise beast_quantize_f32 (mode 0) of params_out.  beast_encode_list_f32 has
+ * the same two envelopes; every other entry point that fits (_rows, _windows,
+ * beast_roundtrip_stats_f32) keeps N <= 16, T <= 256. */
 int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st, int64_t sd, int row_elems,
                      int D, int n_joint, const int32_t* dof_src, const float* proj, int N,
                      const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
@@ -171,10 +172,19 @@ int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st
 
 /* Params-only fit of a LIST of batches in one launch (fit_parameters, reference :181-220,
  * which fits every dataloader batch then takes quantiles): batch i's rows start at the
- * device pointer traj_list[i] (traj_list itself is a device array of nbatch pointers, each
- * 16-byte aligned), every batch has rows_per_batch (a multiple of 8) contiguous rows of
- * [T][row_elems] fp32; params_out [nbatch * rows_per_batch][D*N] (d n).  Same kernel and
- * arithmetic as beast_encode_f32, so params are bitwise those of per-batch calls. */
+ * device pointer traj_list[i] (traj_list itself is a device array of nbatch pointers),
+ * every batch has rows_per_batch (a multiple of 8) contiguous rows of [T][row_elems] fp32;
+ * params_out [nbatch * rows_per_batch][D*N] (d n).  N <= 32, T <= 4096, D <= 64
+ * (BEAST_E_INVALID outside), on beast_encode_f32's two envelopes:
+ *   N <= 16 and T <= 256   k_encode, as beast_encode_f32's contiguous rows: every batch pointer
+ *                          16-byte aligned and T * row_elems a multiple of 4 (BEAST_E_INVALID else);
+ *   beyond either          k_encode_stream_list: the streamed fit with the tile source taken from
+ *                          the table and the chunk pipeline kept full across a workgroup's tiles.
+ *                          Any row length; a batch pointer that is not 16-byte aligned, or
+ *                          T * row_elems off a multiple of 4, costs 4-byte DMA units, nothing else.
+ *                          The chunk is beast_encode_stream_chunk(.., contiguous = 1).
+ * Same arithmetic in the same order as beast_encode_f32 on the same rows, on both envelopes, so
+ * params are bitwise those of per-batch calls. */
 int beast_encode_list_f32(const float* const* traj_list, int nbatch, int64_t rows_per_batch, int T, int row_elems,
                           int D, int n_joint, const int32_t* dof_src, const float* proj, int N, float* params_out,
                           void* stream);
