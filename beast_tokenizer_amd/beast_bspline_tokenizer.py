@@ -891,11 +891,15 @@ class BEASTBsplineTokenizer(TokenizerBase):
         """Can batch ``x`` join ``group`` for one beast_encode_list_f32 launch?  Device-resident
         contiguous fp32 [B, T, D] with B % 8 == 0, all of one shape; inside num_basis <= 16 and
         seq_len <= 256 (the resident kernel) also 16-byte aligned whole-vector rows, which the
-        streamed kernel beyond does not need.  Anything else takes the per-batch path."""
-        if not isinstance(x, torch.Tensor) or self._conditioned or x.dim() != 3:
+        streamed kernel beyond does not need.  Anything else takes the per-batch path, and so does
+        a tokenizer with init / end conditions inside the resident envelope, as it always has;
+        beyond it the conditioned projection P' goes to the list kernel like any other."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
             return False
         p = self._plan()
         streamed = self.num_basis > 16 or p.T > 256
+        if self._conditioned and not streamed:
+            return False
         if (x.device != p.dev or x.dtype is not torch.float32 or not x.is_contiguous() or x.shape[0] == 0
                 or x.shape[0] % 8 or x.shape[1] != p.T or x.shape[2] < p.min_din
                 or (not streamed and (x.data_ptr() % 16 or (x.shape[1] * x.shape[2]) % 4))):
@@ -915,6 +919,8 @@ class BEASTBsplineTokenizer(TokenizerBase):
         out = torch.empty((len(group) * B, self.num_dof * self.num_basis), dtype=torch.float32, device=p.dev)
         _lib.run("beast_encode_list_f32", ptrs.data_ptr(), len(group), B, T, Din, self.num_dof, self.joint_dof,
                  p.p_src, p.p_proj, self.num_basis, out.data_ptr(), _lib.raw_stream(p.idx))
+        if self._conditioned:   # the per-batch path leaves the last batch's conditions behind: so does this
+            self._store_conditions(group[-1], p)
         # the pointer table and the batches may be freed after this: the caching allocators
         # reuse their memory only in the order of the current stream (pinned: after the copy)
         return out

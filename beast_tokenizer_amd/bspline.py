@@ -228,15 +228,34 @@ class DeviceBasis:
         return out
 
     def conditioned_projection(self, times: torch.Tensor, phi_eff: torch.Tensor, proj: torch.Tensor) -> None:
-        """proj[0] (P_eff, f64 [16][Tp]) <- P_eff (I - Dfit^T): the fit of y - pos_det(y)."""
+        """proj[0] (P_eff, f64 [Np][Tp], Np = 16 or 32) <- P_eff (I - Dfit^T): the fit of y - pos_det(y).
+
+        pos_det reads a trajectory at samples 0, 1, T-2 and T-1 only, so Dfit^T has at most four
+        non-zero columns: only the unit trajectories at those samples are pushed through fixed_ctrl /
+        fixed_term (the same sample twice over when T is 2 or 3: a unit trajectory plays every
+        role its sample has), and only those columns of P_eff change.  O(N T) at any T.
+
+        Inside num_basis <= 16 and seq_len <= 256 every sample's unit trajectory is pushed through,
+        as this function always did there: the [N, T] x [T, T] product sums the same terms over t
+        in another order than the [N, T] x [T, 4] one from T of about 255 up (<= 9e-16 apart, the
+        fp32 images equal), and those P' stay the bits they were (Boundary conditions)."""
         T = times.numel()
         full = self.full_basis_at(times).to(torch.float64)                 # [T, C]
-        eye = torch.eye(T, dtype=torch.float64, device=times.device)[:, :, None]   # T unit trajectories, Dj=1
+        dense = self.num_basis <= 16 and T <= 256
+        if dense:
+            unit = torch.eye(T, dtype=torch.float64, device=times.device)[:, :, None]   # T unit trajectories, Dj=1
+        else:
+            cols = sorted({0, 1, T - 2, T - 1})
+            unit = torch.zeros((len(cols), T, 1), dtype=torch.float64, device=times.device)
+            unit[torch.arange(len(cols)), torch.tensor(cols), 0] = 1.0
         dt = (times[1] - times[0]).to(torch.float64)
-        pi, _, _, _, p_init, p_end = self.fixed_ctrl(eye, dt)
-        d = self.fixed_term(full, p_init, p_end, pi, fit=True)[..., 0]      # [T (unit j), T (time t)]
+        pi, _, _, _, p_init, p_end = self.fixed_ctrl(unit, dt)
+        d = self.fixed_term(full, p_init, p_end, pi, fit=True)[..., 0]      # [unit j, T (time t)]
         pe = proj[0, :, :T]
-        proj[0, :, :T] = pe - pe @ d.T
+        if dense:
+            proj[0, :, :T] = pe - pe @ d.T
+        else:
+            proj[0, :, cols] = pe[:, cols] - pe @ d.T
 
     def constants(self, times: torch.Tensor, version: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(Phi [2][T][N] fp32, P [2][Np][Tp] fp64 zero-padded, P in fp32) for a 1-D grid,
@@ -247,10 +266,6 @@ class DeviceBasis:
         if hit is not None:
             return hit
         T, N = times.numel(), self.num_basis
-        if self.conditioned and (N > 16 or T > 256):
-            raise NotImplementedError(
-                f"init_cond_order / end_cond_order != 0 are supported for num_basis <= 16 and seq_len <= 256 "
-                f"(num_basis={N}, seq_len={T}): the streamed kernels fit unconditioned splines only")
         self._drop_stale(times.device, version)
         phi = torch.zeros((2, T, N), dtype=torch.float32, device=times.device)
         phi[: self.n_kinds] = self.basis_at(times.reshape(-1))

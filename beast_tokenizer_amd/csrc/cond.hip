@@ -8,6 +8,8 @@
 //   k_cond_add    reconstruct side: pos[j][t][joint d] += sum_k Phi_full[t][k] ext[j][d][k]
 //                 + init_pos[j][d] over the fixed columns k (get_traj_pos, uni_bspline.py:126-166,
 //                 end order -1 subtracting the end term from column C-2)
+//   k_cond_add_long  the same sum, bit for bit, for T > 256 or C > 20 on a shared basis: tiles of
+//                 trajectories x time rows, the fixed columns staged in LDS, rows moved 16 bytes at a time
 // The fitted columns themselves run in the MFMA kernels of codec.hip with the conditioned
 // projection (bspline.py:DeviceBasis); these replace about a dozen ATen launches per call.
 #include <hip/hip_runtime.h>
@@ -103,6 +105,116 @@ __global__ void k_cond_add(float* __restrict__ pos, int64_t B, int T, int D, con
   *o = __fadd_rn(*o, acc);
 }
 
+// k_cond_add for long trajectories (T > 256 or C > 20) on a shared basis: a workgroup owns a tile
+// of TB trajectories x CH time rows and walks the tiles grid-stride.  Per tile the LDS holds
+//   sB [CH][nf]      the nf <= 4 fixed columns of Phi_full for the chunk's rows (never the whole row)
+//   sW [TB][dj][nf]  each trajectory's fixed control points in column order (end order -1 negated)
+//   sI [TB][dj]      init_pos
+// and, for the kernel's life, sMap [D]: output column -> joint slot, -1 for a gripper column.  A
+// trajectory's chunk is CH * D contiguous floats: it moves as 16-byte loads / stores between its
+// first and last 16-byte boundary and as scalars outside them, whatever D and T are.  Each element
+// takes k_cond_add's terms in k_cond_add's order, so its bits do not depend on the kernel.
+__device__ __forceinline__ float cond_long_term(const float* __restrict__ bt, const float* __restrict__ w, int nf,
+                                                bool has_init, float ip) {
+  float acc = __fmul_rn(bt[0], w[0]);
+  for (int f = 1; f < nf; ++f) acc = __fadd_rn(acc, __fmul_rn(bt[f], w[f]));
+  return has_init ? __fadd_rn(acc, ip) : acc;
+}
+
+__global__ __launch_bounds__(256) void k_cond_add_long(float* __restrict__ pos, int64_t B, int T, int D,
+                                                       const int32_t* __restrict__ jidx, int dj,
+                                                       const float* __restrict__ full, CondArgs c, int CH, int TB,
+                                                       const float* __restrict__ p_init,
+                                                       const float* __restrict__ p_end,
+                                                       const float* __restrict__ init_pos) {
+  extern __shared__ float cond_lds[];
+  const int tid = threadIdx.x;
+  const int ne = c.ec == -1 ? 1 : c.ec;   // fixed end columns read
+  const int nf = c.ic + ne;
+  const bool has_init = c.ic != 0;
+  float* sB = cond_lds;
+  float* sW = sB + CH * nf;
+  float* sI = sW + TB * dj * nf;
+  int* sMap = reinterpret_cast<int*>(sI + TB * dj);
+  for (int i = tid; i < D; i += 256) sMap[i] = -1;
+  __syncthreads();
+  for (int i = tid; i < dj; i += 256) {
+    const int col = jidx[i];
+    if (col >= 0 && col < D) sMap[col] = i;
+  }
+  const int nch = (T + CH - 1) / CH;
+  const int64_t ntiles = ((B + TB - 1) / TB) * nch;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t jt = tile / nch;
+    const int t0 = (int)(tile - jt * nch) * CH;
+    const int rows = min(CH, T - t0);
+    const int64_t j0 = jt * TB;
+    const int nb = (int)min<int64_t>(TB, B - j0);
+    __syncthreads();   // the previous tile's readers are done with sB / sW / sI
+    for (int i = tid; i < rows * nf; i += 256) {
+      const int r = i / nf, f = i - r * nf;
+      const int k = f < c.ic ? f : (c.ec == -1 ? c.C - 2 : c.C - c.ec + (f - c.ic));
+      sB[i] = full[(int64_t)(t0 + r) * c.C + k];
+    }
+    for (int i = tid; i < nb * dj; i += 256) {
+      const int64_t jd = j0 * dj + i;
+      float* w = sW + i * nf;
+      for (int k = 0; k < c.ic; ++k) w[k] = p_init[jd * c.ic + k];
+      if (c.ec == -1) w[c.ic] = -p_end[jd];
+      for (int q = 0; q < c.ec; ++q) w[c.ic + q] = p_end[jd * c.ec + q];
+      if (has_init) sI[i] = init_pos[jd];
+    }
+    __syncthreads();
+    const int n = rows * D;
+    for (int b = 0; b < nb; ++b) {
+      float* base = pos + ((j0 + b) * (int64_t)T + t0) * D;
+      const float* w = sW + b * dj * nf;
+      const float* ip = sI + b * dj;
+      const int head = min(n, (int)((4 - ((reinterpret_cast<uintptr_t>(base) >> 2) & 3)) & 3));
+      const int nvec = (n - head) >> 2;
+      const int tail = head + nvec * 4;
+      if (tid < head + (n - tail)) {   // at most 3 + 3 elements outside the 16-byte body
+        const int l = tid < head ? tid : tail + (tid - head);
+        const int t = l / D;
+        const int d = sMap[l - t * D];
+        if (d >= 0)
+          base[l] = __fadd_rn(base[l], cond_long_term(sB + t * nf, w + d * nf, nf, has_init, has_init ? ip[d] : 0.0f));
+      }
+      for (int v = tid; v < nvec; v += 256) {
+        const int l = head + 4 * v;
+        int t = l / D, col = l - t * D;
+        float4* p4 = reinterpret_cast<float4*>(base + l);
+        const float4 x = *p4;
+        float e[4] = {x.x, x.y, x.z, x.w};
+        bool touched = false;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int d = sMap[col];
+          if (d >= 0) {
+            e[q] = __fadd_rn(e[q], cond_long_term(sB + t * nf, w + d * nf, nf, has_init, has_init ? ip[d] : 0.0f));
+            touched = true;
+          }
+          if (++col == D) { col = 0; ++t; }
+        }
+        if (touched) *p4 = make_float4(e[0], e[1], e[2], e[3]);
+      }
+    }
+  }
+}
+
+// Tile of k_cond_add_long that fits 48 KB of LDS: up to 256 rows x 8 trajectories, trajectories
+// given up first.  False when not even one row of one trajectory fits (k_cond_add serves it).
+bool cond_long_tile(int64_t B, int T, int D, int dj, int nf, int& CH, int& TB, unsigned& lds) {
+  if (D > 4096) return false;
+  auto bytes = [&](int ch, int tb) { return 4 * ((int64_t)ch * nf + (int64_t)tb * dj * (nf + 1) + D); };
+  CH = std::min(T, 256);
+  TB = (int)std::min<int64_t>(B, 8);
+  while (bytes(CH, TB) > 48 * 1024 && TB > 1) TB = (TB + 1) / 2;
+  while (bytes(CH, TB) > 48 * 1024 && CH > 1) CH = (CH + 1) / 2;
+  lds = (unsigned)bytes(CH, TB);
+  return bytes(CH, TB) <= 48 * 1024;
+}
+
 bool cond_orders_ok(int ic, int ec) { return ic >= 0 && ic <= 2 && ec >= -1 && ec <= 2 && (ic != 0 || ec != 0); }
 
 }  // namespace
@@ -145,6 +257,16 @@ extern "C" int beast_cond_add_f32(float* pos, int64_t B, int T, int D, const int
   Queue q;
   BEAST_TRY(queue_of(stream, q, "beast_cond_add_f32"));
   const CondArgs c{init_order, end_order, 0, n_ctrl, 0.0f};
+  // two kernels: k_cond_add (one thread per element) inside T <= 256 and n_ctrl <= 20 and for every
+  // per-trajectory basis; k_cond_add_long (tiles, fixed columns in LDS, 16-byte rows) beyond
+  int CH, TB;
+  unsigned lds;
+  if ((T > 256 || n_ctrl > 20) && full_sb == 0 &&
+      cond_long_tile(B, T, D, dj, init_order + (end_order == -1 ? 1 : end_order), CH, TB, lds)) {
+    const int64_t ntiles = ((B + TB - 1) / TB) * ((T + CH - 1) / CH);
+    return launch<k_cond_add_long>((unsigned)grid_for(ntiles, (int)lds, q.dev), 256, lds, q, "k_cond_add_long", pos, B,
+                                   T, D, joint_idx, dj, full_basis, c, CH, TB, params_init, params_end, init_pos);
+  }
   const int64_t n = B * T * dj;
   return launch<k_cond_add>((unsigned)((n + 255) / 256), 256, 0, q, "k_cond_add", pos, B, T, D, joint_idx, dj,
                             full_basis, full_sb, c, params_init, params_end, init_pos);

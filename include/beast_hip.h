@@ -670,7 +670,14 @@ int beast_roundtrip_stats_f32(const float* traj, int64_t B, int T, int64_t sb, i
  * beast_reconstruct_f32) gains, at the joint DoFs, sum_k full_basis[t][k] * fixed[k] (+ init_pos
  * when init_order > 0) over the fixed columns k (the first init_order, the last |end_order|;
  * end order -1 subtracts params_end from column n_ctrl-2).  full_basis [T][n_ctrl] with
- * full_sb = 0, or per trajectory [B][T][n_ctrl] with full_sb = T * n_ctrl. */
+ * full_sb = 0, or per trajectory [B][T][n_ctrl] with full_sb = T * n_ctrl.
+ * Two kernels, one result: k_cond_add (a thread per element) serves T <= 256 with n_ctrl <= 20
+ * and every per-trajectory basis (full_sb != 0); for T > 256 or n_ctrl > 20 on a shared basis
+ * the host picks k_cond_add_long (tiles of <= 8 trajectories x <= 256 time rows, the <= 4 fixed
+ * columns of the chunk in LDS, 16-byte loads / stores of the position rows, any T, D and
+ * alignment), unless one row of one trajectory does not fit its 48 KB of LDS (dj of several
+ * thousand, or D > 4096).  Both take the same products in the same order: a (b, t, d) result
+ * has the same bits whichever kernel wrote it. */
 int beast_cond_fixed_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st, int64_t sd,
                          const int32_t* joint_idx, int dj, const float* times, const float* knots, int degree,
                          int n_ctrl, float tau, int init_order, int end_order, float* init_pos, float* init_vel,
