@@ -326,8 +326,11 @@ constexpr int RV_WE = BEAST_RV_WE, RV_WR = BEAST_RV_WR, RV_WE_BULK = 8;
 // 209 vs 214 us at B = 262,144, profiles/r05/).  Same products in the same K order with the same
 // even / odd accumulators as k_encode, and the same quantiser, so params and tokens are
 // bit-identical.  With gripper DoFs each kind's chain sees zero B columns for the other kind.
+// Round 12: a 16-wave tile keeps its lane-only values in a table that one wave builds (below), so it
+// has no LDS copies of the bounds and the DoF map; the 8-wave bulk tile keeps them.
+constexpr bool ev_lane_table(int W) { return W > RV_WE_BULK; }
 struct EvSmem {
-  int Y, P, wlo, whi, lcol, pimg, timg, total;
+  int Y, P, wlo, whi, lcol, tab, pimg, timg, total;
 };
 template <class S, int W>
 __host__ __device__ constexpr EvSmem ev_smem(int nkinds) {
@@ -336,12 +339,18 @@ __host__ __device__ constexpr EvSmem ev_smem(int nkinds) {
   int o = 0;
   s.Y = o;    o += round_up(W * PS::T * PS::DL * 4, 1024);
   s.P = o;    o += round_up(nkinds * 16 * PS::Tp * 4, 1024);
-  s.wlo = o;  o += round_up(PS::DN * 4, 256);
-  s.whi = o;  o += round_up(PS::DN * 4, 256);
-  s.lcol = o; o += round_up(PS::D * 4, 256);
+  if (ev_lane_table(W)) {
+    s.tab = o;  o += 4 * 64 * 16;   // lane table: four 16-byte quads per lane, quad-major
+  } else {
+    s.wlo = o;  o += round_up(PS::DN * 4, 256);
+    s.whi = o;  o += round_up(PS::DN * 4, 256);
+    s.lcol = o; o += round_up(PS::D * 4, 256);
+  }
   s.pimg = o; o += W * round_up(PS::DN * 4, 16);
   s.timg = o; o += W * round_up(PS::DN * 8 + 8, 16);   // + one slot the padding lanes write to
-  s.total = o;
+  // A 16-wave tile keeps a CU to itself, as k_reconstruct_v's does (rv_smem): the layout is 78.5 KB,
+  // and the request is padded past 80 KB so that two tiles never share a CU while others idle.
+  s.total = (W == 16 && o <= 84 * 1024) ? 84 * 1024 : o;
   return s;
 }
 
@@ -353,6 +362,21 @@ __host__ __device__ constexpr EvSmem ev_smem(int nkinds) {
 // slot instead of being predicated.  The bounds themselves still arrive by DMA: per-lane global
 // loads of them before the barrier cost more vector-memory issue time than the chain saves
 // (profiles/r07/codec_chain_ab.txt).
+//
+// Round 12 (16-wave tiles): the lane-only values are no longer computed sixteen times per workgroup.
+// One wave (EV_BUILDER) loads its lanes' three (lo, hi) pairs and the DoF's column from global memory
+// -- 7 loads in one wave, where round 7's variant issued them in all sixteen -- computes the slots'
+// quantize_scale (the same function on the same operands: the same bits) and writes, per lane, the
+// operand and token-image offsets without a wave's own part, the bounds and the scales to a 4 KB LDS
+// table in front of the barrier.  After it a wave reads its lanes' entries (four ds_read_b128, quad-
+// major, in the round trip of the fit's operands) and adds its j offsets.  The bounds and DoF-map
+// DMAs and their LDS copies are gone; a params-only call (null bounds) builds the offsets alone.
+// Nothing derived from the bounds or the DoF map outlives the launch.  The 8-wave bulk form keeps
+// round 7's code.
+#ifndef BEAST_EV_BUILDER
+#define BEAST_EV_BUILDER 3
+#endif
+constexpr int EV_BUILDER = BEAST_EV_BUILDER < RV_WE ? BEAST_EV_BUILDER : RV_WE - 1;   // the wave that fills the lane table
 template <class S, int SP, int W>
 __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ traj, int64_t B, EncVArgs a) {
   using PS = VShape<S>;
@@ -366,11 +390,10 @@ __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ t
   constexpr int NQ = 3;   // quantiser slots per lane
   static_assert((T * D) % 4 == 0 && (DN % 2) == 0, "per-trajectory encode: whole 16-byte rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr bool TAB = ev_lane_table(W);
+  static_assert(!TAB || EV_BUILDER < W, "per-trajectory encode: the builder is a wave of the tile");
   float* Y = reinterpret_cast<float*>(smem + L.Y);
   float* P = reinterpret_cast<float*>(smem + L.P);
-  float* wlo = reinterpret_cast<float*>(smem + L.wlo);
-  float* whi = reinterpret_cast<float*>(smem + L.whi);
-  int* lcol = reinterpret_cast<int*>(smem + L.lcol);
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int64_t b0 = (int64_t)blockIdx.x * W;
   const int nb = (int)min<int64_t>(W, B - b0);
@@ -381,46 +404,116 @@ __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ t
   constexpr int tile16 = T * D / 4;   // float4 per trajectory
   dma16<NT>(Y, reinterpret_cast<const float4*>(traj) + b0 * tile16, nb * tile16);
   STAMP(0, 9);
-  dma16<NT>(P, a.proj, nkinds * 4 * Tp);
-  if (quant) {
-    dma4<NT>(wlo, a.w_min, DN);
-    dma4<NT>(whi, a.w_max, DN);
+  // ---- the builder's loads, behind the tile's DMA (which needs the preloaded arguments alone, so no wave
+  //      waits for the argument block in front of it): back, and the table written, while the DMA is in flight
+  int bcol = 0;
+  float blo[NQ] = {0.0f, 0.0f, 0.0f}, bhi[NQ] = {0.0f, 0.0f, 0.0f};
+  if constexpr (TAB) {
+    if (wave == EV_BUILDER) {
+      const int d = min(lane & 15, D - 1);   // lanes lr >= D: the last DoF's column
+      bcol = a.dof_src[d];
+      if (quant) {   // wave-uniform: the bounds pointers are null in a params-only call
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          const int k = d * N + min(slot_row<true>(lane >> 4, u), N - 1);   // clamped for the padding slots
+          blo[u] = a.w_min[k];
+          bhi[u] = a.w_max[k];
+        }
+      }
+    }
   }
-  dma4<NT>(lcol, a.dof_src, D);
-  // ---- lane-only LDS addresses, computed while the DMA is in flight.  Lane (lr, lk): DoF d = lr;
+  dma16<NT>(P, a.proj, nkinds * 4 * Tp);
+  if constexpr (!TAB) {
+    if (quant) {
+      dma4<NT>(smem + L.wlo, a.w_min, DN);
+      dma4<NT>(smem + L.whi, a.w_max, DN);
+    }
+    dma4<NT>(smem + L.lcol, a.dof_src, D);
+  }
+  STAMP(0, 10);
+  // ---- lane-only values, computed while the DMA is in flight.  Lane (lr, lk): DoF d = lr;
   //      slot u holds row n = 4 lk + u, slot 2 of lanes lk >= 2 row 4 (lk - 2) + 3
   const int j = wave;
   const int lr = lane & 15, lk = lane >> 4;
   const bool dok = lr < D;
   const float vm1 = (float)(a.vocab - 1);
   int tq[NQ];   // byte offset of the slot's token in this wave's (n d) image
-  int kq[NQ];   // byte offset of the slot's (d n) column in a bounds array, clamped for the padding slots
+  int yb, yt, pb;
+  float qlo[NQ] = {0.0f, 0.0f, 0.0f}, qhi[NQ] = {0.0f, 0.0f, 0.0f}, qk[NQ] = {0.0f, 0.0f, 0.0f};
+  if constexpr (TAB) {
+    // the builder wave alone, for its 64 lanes and without a wave's own offsets: the operand
+    // addresses with the DoF's column folded in, the token-image slots, and the slots' bounds and
+    // scales (no DMA, no LDS copy of the bounds or of the DoF map)
+    if (wave == EV_BUILDER) {
+      const int c4 = min(max(bcol, 0), D - 1) * 4;
+      int e[16] = {};
+      e[0] = L.Y + lk * D * 4 + c4;
+      e[1] = e[0] + (min(4 * (NST - 1) + lk, T - 1) - lk) * D * 4;   // the last K-step's row, clamped to T - 1
+      e[2] = L.P + (lr * Tp + lk) * 4;
 #pragma unroll
-  for (int u = 0; u < NQ; ++u) {
-    const int n = slot_row<true>(lk, u);
-    kq[u] = (min(lr, D - 1) * N + min(n, N - 1)) * 4;
-    tq[u] = L.timg + (j * TIMG + ((dok && n < N) ? n * D + lr : DN)) * 8;
-    pin(kq[u]); pin(tq[u]);
-  }
-  int yb = L.Y + (j * T * D + lk * D) * 4;
-  int yt = yb + (min(4 * (NST - 1) + lk, T - 1) - lk) * D * 4;   // the last K-step's row, clamped to T - 1
-  int pb = L.P + (lr * Tp + lk) * 4;
-  pin(yb); pin(yt); pin(pb);
-  __syncthreads();
-  STAMP(0, 2);
-  if (j >= nb) return;   // no barrier follows
-  // the DMA's clamped tail filled lcol[D ..] with the last DoF's column: no select for lanes lr >= D
-  const int c4 = min(max(lcol[lr], 0), D - 1) * 4;
-  yb += c4;
-  yt += c4;
-  float qlo[NQ] = {0.0f, 0.0f, 0.0f}, qhi[NQ] = {0.0f, 0.0f, 0.0f};
-  if (quant) {   // wave-uniform; read with the fit's operands
+      for (int u = 0; u < NQ; ++u) {
+        const int n = slot_row<true>(lk, u);
+        e[3 + u] = L.timg + ((dok && n < N) ? n * D + lr : DN) * 8;
+        e[6 + 3 * u] = __float_as_int(blo[u]);
+        e[7 + 3 * u] = __float_as_int(bhi[u]);
+        e[8 + 3 * u] = __float_as_int(beast::quantize_scale(blo[u], bhi[u], vm1));   // unused without bounds
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<int4*>(smem + L.tab + (q * 64 + lane) * 16) =
+            make_int4(e[4 * q], e[4 * q + 1], e[4 * q + 2], e[4 * q + 3]);
+    }
+    STAMP(0, 11);
+    __syncthreads();
+    STAMP(0, 2);
+    if (j >= nb) return;   // no barrier follows
+    // the lane's entry, read in the round trip of the fit's operands; this wave's offsets added
+    int e[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int4 v = *reinterpret_cast<const int4*>(smem + L.tab + (q * 64 + lane) * 16);
+      e[4 * q] = v.x; e[4 * q + 1] = v.y; e[4 * q + 2] = v.z; e[4 * q + 3] = v.w;
+    }
+    yb = e[0] + j * T * D * 4;
+    yt = e[1] + j * T * D * 4;
+    pb = e[2];
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
-      qlo[u] = *reinterpret_cast<const float*>(smem + L.wlo + kq[u]);
-      qhi[u] = *reinterpret_cast<const float*>(smem + L.whi + kq[u]);
+      tq[u] = e[3 + u] + j * TIMG * 8;
+      qlo[u] = __int_as_float(e[6 + 3 * u]);
+      qhi[u] = __int_as_float(e[7 + 3 * u]);
+      qk[u] = __int_as_float(e[8 + 3 * u]);
+    }
+  } else {
+    int kq[NQ];   // byte offset of the slot's (d n) column in a bounds array, clamped for the padding slots
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      const int n = slot_row<true>(lk, u);
+      kq[u] = (min(lr, D - 1) * N + min(n, N - 1)) * 4;
+      tq[u] = L.timg + (j * TIMG + ((dok && n < N) ? n * D + lr : DN)) * 8;
+      pin(kq[u]); pin(tq[u]);
+    }
+    yb = L.Y + (j * T * D + lk * D) * 4;
+    yt = yb + (min(4 * (NST - 1) + lk, T - 1) - lk) * D * 4;   // the last K-step's row, clamped to T - 1
+    pb = L.P + (lr * Tp + lk) * 4;
+    pin(yb); pin(yt); pin(pb);
+    STAMP(0, 11);
+    __syncthreads();
+    STAMP(0, 2);
+    if (j >= nb) return;   // no barrier follows
+    // the DMA's clamped tail filled lcol[D ..] with the last DoF's column: no select for lanes lr >= D
+    const int c4 = min(max(reinterpret_cast<const int*>(smem + L.lcol)[lr], 0), D - 1) * 4;
+    yb += c4;
+    yt += c4;
+    if (quant) {   // wave-uniform; read with the fit's operands
+#pragma unroll
+      for (int u = 0; u < NQ; ++u) {
+        qlo[u] = *reinterpret_cast<const float*>(smem + L.wlo + kq[u]);
+        qhi[u] = *reinterpret_cast<const float*>(smem + L.whi + kq[u]);
+      }
     }
   }
+  STAMP(0, 12);
   // ---- fit: lane (lr, lk): A = P_kind[n = lr][t = 4 st + lk], B = y[j][t][lcol[d = lr]] (t clamped
   //      to T - 1: the zero-padded P columns meet those rows), even / odd steps accumulate apart.
   //      B columns d >= D are never stored, so with one kind they need no zeroing.
@@ -462,7 +555,8 @@ __global__ __launch_bounds__(W * 64) void k_encode_v(const float* __restrict__ t
     float qv[NQ];
     int bin[NQ];
     slot_values<true>(pv, qv);
-    beast::quantize_bins(qv, qlo, qhi, vm1, bin);
+    if constexpr (TAB) beast::quantize_bins(qv, qlo, qhi, vm1, bin, qk);   // the builder's scales
+    else beast::quantize_bins(qv, qlo, qhi, vm1, bin);
     if (a.tok_offset == 0) {   // wave-uniform: no 64-bit add
 #pragma unroll
       for (int u = 0; u < NQ; ++u) *reinterpret_cast<long long*>(smem + tq[u]) = beast::widen_bin(bin[u], 0ull);

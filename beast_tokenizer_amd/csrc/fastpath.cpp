@@ -10,6 +10,7 @@
 // takes the general Python path, which raises the reference's exception types.
 #include <torch/extension.h>
 #include <torch/csrc/autograd/python_variable.h>
+#include <ATen/hip/EmptyTensor.h>
 #include <c10/hip/HIPStream.h>
 
 #include <algorithm>
@@ -32,9 +33,16 @@ typedef const char* (*err_fn_t)(void);
 // (tokens first, params at byte 8*B*DN): one allocator round trip per encode instead of two
 // (the B = 4,096 step is at the host / GPU crossover).  Each tensor is a plain
 // TensorImpl over the shared storage, sized directly -- no narrow / dtype-view chain.
-inline void alloc_enc_outputs(const at::Tensor& like, int64_t B, int64_t DN, at::Tensor& tokens, at::Tensor& params) {
+// Uninitialised device memory straight from the caching allocator (at::detail::empty_cuda): what
+// at::empty(sizes, options) arrives at after building TensorOptions and going through the dispatcher.
+inline at::Tensor empty_on(int64_t device, at::IntArrayRef sizes, at::ScalarType dtype) {
+  return at::Tensor(at::detail::empty_cuda(sizes, dtype, c10::Device(c10::kCUDA, (c10::DeviceIndex)device),
+                                           std::nullopt));
+}
+
+inline void alloc_enc_outputs(int64_t device, int64_t B, int64_t DN, at::Tensor& tokens, at::Tensor& params) {
   const int64_t n = B * DN;
-  at::Tensor buf = at::empty({n * 12}, like.options().dtype(at::kByte));
+  at::Tensor buf = empty_on(device, {n * 12}, at::kByte);
   const c10::Storage& st = buf.storage();
   tokens = at::detail::make_tensor<c10::TensorImpl>(c10::Storage(st), buf.key_set(),
                                                      caffe2::TypeMeta::Make<int64_t>());
@@ -128,9 +136,15 @@ struct Plan {
     t0 = clk::now();
     for (int64_t i = 0; i < n; ++i) {
       at::Tensor p, t;
-      alloc_enc_outputs(x, B, DN, t, p);
+      alloc_enc_outputs(device, B, DN, t, p);
     }
     out["alloc1_shared"] = us(t0);
+    t0 = clk::now();
+    for (int64_t i = 0; i < n; ++i) at::Tensor b = at::empty({B * DN * 12}, x.options().dtype(at::kByte));
+    out["alloc1_dispatched"] = us(t0);
+    t0 = clk::now();
+    for (int64_t i = 0; i < n; ++i) at::Tensor b = empty_on(device, {B * DN * 12}, at::kByte);
+    out["alloc1_direct"] = us(t0);
     at::Tensor params = at::empty({B, DN}, x.options());
     at::Tensor tokens = at::empty({B, DN}, x.options().dtype(at::kLong));
     t0 = clk::now();
@@ -255,7 +269,7 @@ PyObject* fast_encode(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   at::Tensor params, tokens;
   try {
     const int64_t B = x.size(0), DN = p->D * p->N;
-    alloc_enc_outputs(x, B, DN, tokens, params);
+    alloc_enc_outputs(p->device, B, DN, tokens, params);
     const hipStream_t st = c10::hip::getCurrentHIPStream(p->device).stream();
     const int rc = p->enc(x.data_ptr<float>(), B, (int)p->T, x.stride(0), x.stride(1), x.stride(2), (int)x.size(2),
                           (int)p->D, (int)p->nj, reinterpret_cast<const int32_t*>(p->p_src),
@@ -307,7 +321,7 @@ PyObject* fast_reconstruct(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   else Py_RETURN_NONE;
   at::Tensor pos;
   try {
-    pos = at::empty({B, p->T, p->D}, tok.options().dtype(at::kFloat));
+    pos = empty_on(p->device, {B, p->T, p->D}, at::kFloat);
     const hipStream_t st = c10::hip::getCurrentHIPStream(p->device).stream();
     const int rc = p->rec(tok.data_ptr<int64_t>(), B, (int)p->D, (int)p->nj, (int)p->N, (int)p->V, offset,
                           reinterpret_cast<const float*>(p->p_wmn), reinterpret_cast<const float*>(p->p_wmx),

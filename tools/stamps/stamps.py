@@ -17,6 +17,10 @@ sys.path.insert(0, REPO)
 NW = 16   # stamp slots per kernel (waves per workgroup <= 16; g_stamps[2][16][16] in csrc/codec_device.h, part of codec.hip)
 ENC = ["start", "issued", "landed", "mfma_done", "pb_ready", "params_stored", "tokens_stored", "drained", "acc_ready",
        "y_dma", "p_dma", "small_dma", "t2_landed", "t2_mfma_done", "t2_tokens_stored"]
+# k_encode_v (the fixed shapes' per-trajectory encode): "issued" is every DMA issued, "lane_done" the arrival
+# at the tile barrier (the lane-only block, or the lane table, done), "operands_ready" the bounds / table entry read
+ENC_V = ["start", "-", "landed", "mfma_done", "-", "images_ready", "-", "stores_issued", "drained", "y_dma",
+         "issued", "lane_done", "operands_ready"]
 REC = ["start", "issued", "landed", "decoded", "w_ready", "mfma_done", "ob_ready", "stored", "drained",
        "tok_dma", "small_dma", "phi_loads", "lut",
        # k_reconstruct_v's prologue: every DMA issued, the inline lane-only values done, the lane table written
@@ -108,10 +112,8 @@ def main():
             return lib.beast_reconstruct_f32(tokens.data_ptr(), B, 14, 14, 10, 256, 0, p.p_wmn, p.p_wmx, p.p_phi, 0,
                                              50, p.p_dst, 14, None, 0, None, None, pos.data_ptr(), None, s)
         res = {}
-        pipe = ["start", "dma_issued", "A_landed", "fitA_done(mw)", "B_landed(mw)", "fitB_done|storeA_done", "bar3",
-                "storeB_issued", "drained"]
-        for kname, fn, names, k in (("encode", enc, pipe if B <= 8192 else ENC, 0),
-                                    ("encode_params_only", enc_params_only, pipe if B <= 8192 else ENC, 0),
+        for kname, fn, names, k in (("encode", enc, ENC_V, 0),
+                                    ("encode_params_only", enc_params_only, ENC_V, 0),
                                     ("reconstruct", rec, REC, 1)):
             for _ in range(20):           # warm: code, constants and the tile in L2 as in back-to-back use
                 assert fn() == 0
