@@ -21,7 +21,7 @@ BEAST_E_INVALID = -1
 BEAST_E_HIP = -2
 BEAST_E_UNSUPPORTED = -3
 BEAST_E_WORKSPACE = -4
-ABI_VERSION = 7
+ABI_VERSION = 8
 OPT_GENERIC_KERNELS = 1
 OPT_BLOCK_WAVES = 2
 OPT_MERGE_LDS_MIN = 3
@@ -79,6 +79,7 @@ SIGNATURES = {
     "beast_reconstruct_stream_rows": (_i32, [_i32, _i32, _i32, _i32, _i32]),
     "beast_reconstruct_derivs_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp,
                                             _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "beast_reconstruct_derivs_stream_rows": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "beast_reconstruct_derivs_bwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32,
                                                 _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "beast_logits_expect": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp]),

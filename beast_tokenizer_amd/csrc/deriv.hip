@@ -16,6 +16,10 @@
 // the output row wraps), so LDS serves one W row per element and one set of basis rows per
 // four.  Tiles are 16 trajectories and the resident workgroups stride over them; a batch too
 // small to give every CU two such tiles takes tiles of 4, one per workgroup.
+//
+//   k_reconstruct_derivs_stream  (deriv_stream.h) the same products for shared slabs too large to
+//                         stage whole: the slabs stream through two LDS buffers in chunks of output
+//                         rows, and the time axis is cut across workgroups where tiles are few
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,7 +65,8 @@ struct DerivArgs {
 __device__ __forceinline__ int small_div(int x, float inv_d) { return (int)(((float)x + 0.5f) * inv_d); }
 
 // one output element of every requested order with the basis rows read from memory (per-row
-// grids, or shared slabs too large for LDS): a sequential fma over n, as k_reconstruct_rows
+// grids; shared slabs too large for LDS stream, deriv_stream.h): a sequential fma over n, as
+// k_reconstruct_rows
 __device__ __forceinline__ void deriv_dot_mem(const DerivArgs& a, const float* __restrict__ Wr, int kind,
                                               int64_t b, int t, float (&v)[DV_ORDERS]) {
   const int64_t slab = (int64_t)2 * a.Tout * a.N;
@@ -250,7 +255,14 @@ int launch_derivs_ks(const DerivArgs& a, bool lb, int phi_bytes, const Queue& q)
 
 }  // namespace
 
+#include "deriv_stream.h"
+
 // =================================================================== C-ABI ==
+extern "C" int beast_reconstruct_derivs_stream_rows(int T_out, int D, int n_joint, int N, int num_dof_out,
+                                                    int orders_mask) {
+  return ds_rows(T_out, D, n_joint, N, num_dof_out, orders_mask);
+}
+
 extern "C" int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, int D, int n_joint, int N, int vocab,
                                             int64_t tok_offset, const float* w_min, const float* w_max,
                                             const float* basis, int64_t basis_sb, int T_out,
@@ -292,6 +304,16 @@ extern "C" int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, in
   const bool lb = basis_sb == 0 && (int64_t)phi_floats * 4 <= DV_BASIS_LDS;
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_reconstruct_derivs_f32")) return rc;
+  // shared slabs that do not fit DV_BASIS_LDS stream in chunks of ds_rows() output rows
+  const int mask = (pos_out ? 1 : 0) | (vel_out ? 2 : 0) | (acc_out ? 4 : 0);
+  if (const int rows = basis_sb == 0 ? ds_rows(T_out, D, n_joint, N, num_dof_out, mask) : 0) {
+    switch (KS) {
+      case 1: return launch_derivs_stream<1>(a, rows, mask, q);
+      case 2: return launch_derivs_stream<2>(a, rows, mask, q);
+      case 3: return launch_derivs_stream<3>(a, rows, mask, q);
+      default: return launch_derivs_stream<4>(a, rows, mask, q);
+    }
+  }
   switch (KS) {
     case 1: return launch_derivs_ks<1>(a, lb, phi_floats * 4, q);
     case 2: return launch_derivs_ks<2>(a, lb, phi_floats * 4, q);

@@ -41,12 +41,13 @@ extern "C" {
 #define BEAST_E_UNSUPPORTED (-3) /* shape outside the kernels' envelope       */
 #define BEAST_E_WORKSPACE (-4)   /* workspace too small                       */
 
-#define BEAST_ABI_VERSION 7   /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
+#define BEAST_ABI_VERSION 8  /* 2: beast_xent_rows, beast_xent_rows_bwd; 3: beast_sample_rows;
                                  4: beast_score_rows, beast_score_rows_bwd; 5: beast_encode_windows_f32;
                                  6: beast_reconstruct_windows_f32, beast_blend_candidates_host,
                                     beast_blend_member_host;
                                  7: beast_encode_stream_chunk, beast_reconstruct_stream_rows, the
-                                    [Np][Tp] projection layout and N <= 32 / T <= 4096 */
+                                    [Np][Tp] projection layout and N <= 32 / T <= 4096;
+                                 8: beast_reconstruct_derivs_stream_rows */
 
 int beast_abi_version(void);
 const char* beast_last_error(void);
@@ -373,7 +374,12 @@ int beast_reconstruct_stream_rows(int T_out, int D, int n_joint, int N, int num_
  *               Gripper DoFs (d >= n_joint, degree 0) get 0 in vel_out and acc_out whatever
  *               their slab holds.
  * Tokens are read and dequantised once per trajectory; every requested order is written from
- * that copy.  N <= 16, D <= 64, T_out <= 4096, num_dof_out <= 4096, else BEAST_E_UNSUPPORTED. */
+ * that copy.  N <= 16, D <= 64, T_out <= 4096, num_dof_out <= 4096, else BEAST_E_UNSUPPORTED.
+ * A shared basis (basis_sb == 0) whose requested slabs, padded to 4 ceil(N / 4) columns, fit 48 KB
+ * is staged in LDS whole; a larger one (a dense time grid: T_out >= 342 at N = 10 with all three
+ * outputs) moves through LDS in chunks of beast_reconstruct_derivs_stream_rows() output rows, and
+ * a batch too small to fill the GPU is split along the time axis as well.  Either way an output
+ * element is the same fma chain over n: the bits do not depend on the path. */
 int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, int D, int n_joint, int N, int vocab,
                                  int64_t tok_offset, const float* w_min, const float* w_max,
                                  const float* basis, int64_t basis_sb, int T_out,
@@ -381,6 +387,14 @@ int beast_reconstruct_derivs_f32(const int64_t* tokens, int64_t B, int D, int n_
                                  const float* init_p, int64_t init_p_sb, const int32_t* init_p_src,
                                  float* pos_out, float* vel_out, float* acc_out, const float* ntokens,
                                  void* stream);
+
+/* Host only, no launch: output rows per chunk that beast_reconstruct_derivs_f32 streams a shared
+ * basis with (the dispatch calls the same function), a positive multiple of 4; bit o of
+ * orders_mask stands for a non-null output o (1 pos_out, 2 vel_out, 4 acc_out).  It depends on
+ * T_out only through the 0: 0 where the slabs fit LDS whole (the resident kernel serves the shape)
+ * and for arguments beast_reconstruct_derivs_f32 rejects.  A row range shorter than the chunk (the
+ * time axis split over workgroups, or T_out below it) is one chunk. */
+int beast_reconstruct_derivs_stream_rows(int T_out, int D, int n_joint, int N, int num_dof_out, int orders_mask);
 
 /* The adjoint of beast_reconstruct_derivs_f32 on its ntokens path, in ONE launch: upstream
  * gradients of the positions, velocities and accelerations -> the gradient of the normalised
