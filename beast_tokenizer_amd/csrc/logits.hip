@@ -41,7 +41,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "launch.h"
@@ -1895,17 +1895,6 @@ __global__ __launch_bounds__(LG_THREADS) void k_score_bwd_long(ScoreArgs a) {
 }
 
 // ------------------------------------------------------------------------ launching --
-// Diagnostic knob: BEAST_DEBUG_LOGITS_ROWS=<1|2|4> rows a wave works on at once (timing tools);
-// default 4 (tests/tools/logits_timing.py).  Results do not depend on it.
-inline int rows_in_flight() {
-  static const int v = [] {
-    const char* e = getenv("BEAST_DEBUG_LOGITS_ROWS");
-    const int r = e ? atoi(e) : 4;
-    return (r == 1 || r == 2 || r == 4) ? r : 4;
-  }();
-  return v;
-}
-
 // Workgroups of K resident on the stream's device (launch.h's occupancy query, asked once per
 // kernel and device).
 template <auto K>
@@ -1934,58 +1923,64 @@ int run_rows(const Args& a, const Queue& q, const char* what, int64_t* resident_
   return launch<K>((unsigned)grid, LG_THREADS, 0, q, what, a);
 }
 
-template <class T>
-int run_forward(const LogitsArgs& a, const Queue& q, int64_t* resident_rows) {
-  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
-  const int r = rows_in_flight();
-  const char* what = "k_logits_expect";
-  if (chunks == 1) {
-    if (r == 1) return run_rows<k_logits_expect<T, 1, 1>, 1>(a, q, what, resident_rows);
-    if (r == 2) return run_rows<k_logits_expect<T, 1, 2>, 2>(a, q, what, resident_rows);
-    return run_rows<k_logits_expect<T, 1, 4>, 4>(a, q, what, resident_rows);
-  }
-  if (chunks == 2) {
-    if (r == 1) return run_rows<k_logits_expect<T, 2, 1>, 1>(a, q, what, resident_rows);
-    return run_rows<k_logits_expect<T, 2, 2>, 2>(a, q, what, resident_rows);
-  }
-  if (chunks <= LG_MAX_CHUNKS) return run_rows<k_logits_expect<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, resident_rows);
-  return run_rows<k_logits_expect_online<T>, 1>(a, q, "k_logits_expect_online", resident_rows);
+// The ladder, for every family: rows of `chunks` wave-loads take resident(RowForm<NCH, R>{}), the
+// register form with R rows in flight (4 / 2 / 1: DESIGN.md §4), up to LG_MAX_CHUNKS and streaming()
+// beyond.  No GPU test can see which form served a row (its outputs are bitwise the same under
+// every R), so the static_asserts pin it: form_code is 10 NCH + R, 0 for the streaming form.
+template <int NCH, int R>
+struct RowForm {
+  static constexpr int nch = NCH, r = R;
+};
+template <class Resident, class Streaming>
+constexpr auto for_chunks(int chunks, Resident&& resident, Streaming&& streaming) {
+  if (chunks == 1) return resident(RowForm<1, 4>{});
+  if (chunks == 2) return resident(RowForm<2, 2>{});
+  if (chunks <= LG_MAX_CHUNKS) return resident(RowForm<LG_MAX_CHUNKS, 1>{});
+  return streaming();
 }
-
-template <class T>
-int run_backward(const LogitsArgs& a, const Queue& q, int64_t* resident_rows) {
-  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
-  const int r = rows_in_flight();
-  const char* what = "k_logits_expect_bwd";
-  if (chunks == 1) {
-    if (r == 1) return run_rows<k_logits_expect_bwd<T, 1, 1>, 1>(a, q, what, resident_rows);
-    if (r == 2) return run_rows<k_logits_expect_bwd<T, 1, 2>, 2>(a, q, what, resident_rows);
-    return run_rows<k_logits_expect_bwd<T, 1, 4>, 4>(a, q, what, resident_rows);
-  }
-  if (chunks == 2) {
-    if (r == 1) return run_rows<k_logits_expect_bwd<T, 2, 1>, 1>(a, q, what, resident_rows);
-    return run_rows<k_logits_expect_bwd<T, 2, 2>, 2>(a, q, what, resident_rows);
-  }
-  if (chunks <= LG_MAX_CHUNKS) return run_rows<k_logits_expect_bwd<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, resident_rows);
-  return run_rows<k_logits_expect_bwd_long<T>, 1>(a, q, "k_logits_expect_bwd_long", resident_rows);
+constexpr int row_chunks(int V, int epl) { return (V + 64 * epl - 1) / (64 * epl); }
+constexpr int form_code(int V, int epl) {
+  return for_chunks(row_chunks(V, epl), [](auto f) { return 10 * f.nch + f.r; }, [] { return 0; });
 }
+constexpr int LG_WIDEST = 10 * LG_MAX_CHUNKS + 1;
+static_assert(form_code(1, 1) == 14 && form_code(65, 1) == 22 && form_code(129, 1) == LG_WIDEST &&
+              form_code(193, 1) == LG_WIDEST && form_code(257, 1) == 0);                 // 1, 2, 3, 4, 5 chunks
+template <int E>
+constexpr bool ladder_edges =
+    form_code(64 * E, E) == 14 && form_code(64 * E + 1, E) == 22 && form_code(128 * E, E) == 22 &&
+    form_code(128 * E + 1, E) == LG_WIDEST && form_code(256 * E, E) == LG_WIDEST && form_code(256 * E + 1, E) == 0;
+static_assert(ladder_edges<ElemF32::EPL> && ladder_edges<ElemF16::EPL> && ladder_edges<ElemBF16::EPL>);
 
-int run_typed(int dtype, bool backward, const LogitsArgs& a, const Queue& q, int64_t* resident_rows) {
+// f(ElemF32{} / ElemF16{} / ElemBF16{}) for a dtype code check_common has accepted.
+template <class F>
+int with_elem(int dtype, F&& f) {
   switch (dtype) {
-    case BEAST_LOGITS_F32:
-      return backward ? run_backward<ElemF32>(a, q, resident_rows) : run_forward<ElemF32>(a, q, resident_rows);
-    case BEAST_LOGITS_F16:
-      return backward ? run_backward<ElemF16>(a, q, resident_rows) : run_forward<ElemF16>(a, q, resident_rows);
-    default:
-      return backward ? run_backward<ElemBF16>(a, q, resident_rows) : run_forward<ElemBF16>(a, q, resident_rows);
+    case BEAST_LOGITS_F32: return f(ElemF32{});
+    case BEAST_LOGITS_F16: return f(ElemF16{});
+    default: return f(ElemBF16{});
   }
+}
+
+int run_expect(int dtype, bool backward, const LogitsArgs& a, const Queue& q, int64_t* resident_rows) {
+  return with_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    const int chunks = row_chunks(a.V, T::EPL);
+    if (backward)
+      return for_chunks(
+          chunks,
+          [&](auto f) { return run_rows<k_logits_expect_bwd<T, f.nch, f.r>, f.r>(a, q, "k_logits_expect_bwd", resident_rows); },
+          [&] { return run_rows<k_logits_expect_bwd_long<T>, 1>(a, q, "k_logits_expect_bwd_long", resident_rows); });
+    return for_chunks(
+        chunks, [&](auto f) { return run_rows<k_logits_expect<T, f.nch, f.r>, f.r>(a, q, "k_logits_expect", resident_rows); },
+        [&] { return run_rows<k_logits_expect_online<T>, 1>(a, q, "k_logits_expect_online", resident_rows); });
+  });
 }
 
 // K as the kernels take it: B * K where the B batch elements lie K token strides apart (or there
 // is only one), so that a row's offset is row * sk.
 int64_t folded_k(int64_t B, int K, int64_t sb, int64_t sk) { return (B == 1 || sb == K * sk) ? B * K : K; }
 
-// The checks both directions share (before any HIP call).
+// The checks every entry point shares (before any HIP call).
 int check_common(const char* fn, const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
                  float temperature) {
   BEAST_REQUIRE(logits != nullptr, "%s: null logits", fn);
@@ -2000,30 +1995,26 @@ int check_common(const char* fn, const void* logits, int dtype, int64_t B, int K
   return BEAST_OK;
 }
 
-// The cross-entropy kernels: rows in flight per chunk count are the decode kernels' defaults.
-template <class T>
-int run_xent(bool backward, const XentArgs& a, const Queue& q) {
-  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
-  if (backward) {
-    const char* what = "k_xent_bwd";
-    if (chunks == 1) return run_rows<k_xent_bwd<T, 1, 4>, 4>(a, q, what, nullptr);
-    if (chunks == 2) return run_rows<k_xent_bwd<T, 2, 2>, 2>(a, q, what, nullptr);
-    if (chunks <= LG_MAX_CHUNKS) return run_rows<k_xent_bwd<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, nullptr);
-    return run_rows<k_xent_bwd_long<T>, 1>(a, q, "k_xent_bwd_long", nullptr);
-  }
-  const char* what = "k_xent";
-  if (chunks == 1) return run_rows<k_xent<T, 1, 4>, 4>(a, q, what, nullptr);
-  if (chunks == 2) return run_rows<k_xent<T, 2, 2>, 2>(a, q, what, nullptr);
-  if (chunks <= LG_MAX_CHUNKS) return run_rows<k_xent<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, nullptr);
-  return run_rows<k_xent_online<T>, 1>(a, q, "k_xent_online", nullptr);
+// The fields all four argument blocks share; everything else zero.
+template <class Args>
+Args row_args(const void* logits, int64_t B, int K, int V, int64_t sb, int64_t sk) {
+  Args a{};
+  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  return a;
 }
 
-int run_xent_typed(int dtype, bool backward, const XentArgs& a, const Queue& q) {
-  switch (dtype) {
-    case BEAST_LOGITS_F32: return run_xent<ElemF32>(backward, a, q);
-    case BEAST_LOGITS_F16: return run_xent<ElemF16>(backward, a, q);
-    default: return run_xent<ElemBF16>(backward, a, q);
-  }
+int run_xent(int dtype, bool backward, const XentArgs& a, const Queue& q) {
+  return with_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    const int chunks = row_chunks(a.V, T::EPL);
+    if (backward)
+      return for_chunks(
+          chunks, [&](auto f) { return run_rows<k_xent_bwd<T, f.nch, f.r>, f.r>(a, q, "k_xent_bwd", nullptr); },
+          [&] { return run_rows<k_xent_bwd_long<T>, 1>(a, q, "k_xent_bwd_long", nullptr); });
+    return for_chunks(
+        chunks, [&](auto f) { return run_rows<k_xent<T, f.nch, f.r>, f.r>(a, q, "k_xent", nullptr); },
+        [&] { return run_rows<k_xent_online<T>, 1>(a, q, "k_xent_online", nullptr); });
+  });
 }
 
 // The checks both cross-entropy directions share (before any HIP call), and the arguments they share.
@@ -2039,92 +2030,92 @@ int check_xent(const char* fn, const void* logits, int dtype, int64_t B, int K, 
 
 XentArgs xent_args(const void* logits, int64_t B, int K, int V, int64_t sb, int64_t sk, const int64_t* target_tok,
                    const float* target_pos, int64_t tok_offset, int64_t ignore_index, float smoothing) {
-  XentArgs a{};
-  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  XentArgs a = row_args<XentArgs>(logits, B, K, V, sb, sk);
   a.vm1 = (float)(V - 1);
   a.tok = target_tok; a.pos = target_pos; a.tok_offset = tok_offset; a.ignore_index = ignore_index;
   a.eps = smoothing; a.keep = 1.0f - smoothing; a.eps_v = smoothing / (float)V;
   return a;
 }
 
-// The sampling kernels: rows in flight per chunk count are the decode kernels' defaults; the
-// truncating form only where a truncation is asked for.
-template <class T>
-int run_sample(const SampleArgs& a, bool trunc, const Queue& q) {
-  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
-  const char* what = "k_sample";
-  if (chunks > LG_MAX_CHUNKS) return run_rows<k_sample_long<T>, 1>(a, q, "k_sample_long", nullptr);
-  if (trunc) {
-    if (chunks == 1) return run_rows<k_sample<T, 1, 4, true>, 4>(a, q, what, nullptr);
-    if (chunks == 2) return run_rows<k_sample<T, 2, 2, true>, 2>(a, q, what, nullptr);
-    return run_rows<k_sample<T, LG_MAX_CHUNKS, 1, true>, 1>(a, q, what, nullptr);
-  }
-  if (chunks == 1) return run_rows<k_sample<T, 1, 4, false>, 4>(a, q, what, nullptr);
-  if (chunks == 2) return run_rows<k_sample<T, 2, 2, false>, 2>(a, q, what, nullptr);
-  return run_rows<k_sample<T, LG_MAX_CHUNKS, 1, false>, 1>(a, q, what, nullptr);
+// The sampling and the scoring forward have a TRUNC axis: the truncating form only where a
+// truncation is asked for, and never beyond LG_MAX_CHUNKS chunks (check_truncation).
+template <class F>
+int with_trunc(bool trunc, F&& f) {
+  return trunc ? f(std::true_type{}) : f(std::false_type{});
+}
+
+int run_sample(int dtype, const SampleArgs& a, bool trunc, const Queue& q) {
+  return with_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    return with_trunc(trunc, [&](auto tr) {
+      return for_chunks(
+          row_chunks(a.V, T::EPL),
+          [&](auto f) { return run_rows<k_sample<T, f.nch, f.r, decltype(tr)::value>, f.r>(a, q, "k_sample", nullptr); },
+          [&] { return run_rows<k_sample_long<T>, 1>(a, q, "k_sample_long", nullptr); });
+    });
+  });
 }
 
 constexpr int SAMPLE_MAX_S = 64;      // one draw per lane
 
-// The scoring kernels: rows in flight and the truncating form as for the sampling kernels.
-template <class T>
-int run_score(bool backward, const ScoreArgs& a, bool trunc, const Queue& q) {
-  const int chunks = (a.V + 64 * T::EPL - 1) / (64 * T::EPL);
-  if (backward) {
-    const char* what = "k_score_bwd";
-    if (chunks == 1) return run_rows<k_score_bwd<T, 1, 4>, 4>(a, q, what, nullptr);
-    if (chunks == 2) return run_rows<k_score_bwd<T, 2, 2>, 2>(a, q, what, nullptr);
-    if (chunks <= LG_MAX_CHUNKS) return run_rows<k_score_bwd<T, LG_MAX_CHUNKS, 1>, 1>(a, q, what, nullptr);
-    return run_rows<k_score_bwd_long<T>, 1>(a, q, "k_score_bwd_long", nullptr);
-  }
-  const char* what = "k_score";
-  if (chunks > LG_MAX_CHUNKS) return run_rows<k_score_long<T>, 1>(a, q, "k_score_long", nullptr);
-  if (trunc) {
-    if (chunks == 1) return run_rows<k_score<T, 1, 4, true>, 4>(a, q, what, nullptr);
-    if (chunks == 2) return run_rows<k_score<T, 2, 2, true>, 2>(a, q, what, nullptr);
-    return run_rows<k_score<T, LG_MAX_CHUNKS, 1, true>, 1>(a, q, what, nullptr);
-  }
-  if (chunks == 1) return run_rows<k_score<T, 1, 4, false>, 4>(a, q, what, nullptr);
-  if (chunks == 2) return run_rows<k_score<T, 2, 2, false>, 2>(a, q, what, nullptr);
-  return run_rows<k_score<T, LG_MAX_CHUNKS, 1, false>, 1>(a, q, what, nullptr);
+// The truncation checks of the sampling and scoring entry points, in two steps because each entry
+// point checks its own pointers between them: the ranges (S in [min_S, SAMPLE_MAX_S]) ...
+int check_truncation_ranges(const char* fn, int top_k, float top_p, int S, int min_S) {
+  BEAST_REQUIRE(top_k >= 0, "%s: top_k must be >= 0 (got %d)", fn, top_k);
+  BEAST_REQUIRE(top_p > 0.0f && top_p <= 1.0f, "%s: top_p must lie in (0, 1] (got %g)", fn, (double)top_p);
+  BEAST_REQUIRE(S >= min_S && S <= SAMPLE_MAX_S, "%s: S must lie in [%d, %d] (got %d)", fn, min_S, SAMPLE_MAX_S, S);
+  return BEAST_OK;
+}
+// ... and the bound on V.  `trunc`: a truncation truncates (the TRUNC kernels); `top_k` becomes what
+// the kernels take, 0 where it keeps every bin.
+int check_truncation(const char* fn, int dtype, int V, int& top_k, float top_p, bool& trunc) {
+  top_k = (top_k > 0 && top_k < V) ? top_k : 0;
+  trunc = top_k > 0 || top_p < 1.0f;
+  const int epl = dtype == BEAST_LOGITS_F32 ? ElemF32::EPL : ElemF16::EPL;
+  BEAST_REQUIRE_CODE(!trunc || V <= LG_MAX_CHUNKS * 64 * epl, BEAST_E_UNSUPPORTED,
+                     "%s supports top_k / top_p for V <= %d of this dtype (V=%d)", fn, LG_MAX_CHUNKS * 64 * epl, V);
+  return BEAST_OK;
 }
 
-// The checks both scoring directions share (before any HIP call); `trunc`: a truncation truncates.
+// The backward reads the forward's threshold from stats: no TRUNC axis.
+int run_score(int dtype, bool backward, const ScoreArgs& a, bool trunc, const Queue& q) {
+  return with_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    const int chunks = row_chunks(a.V, T::EPL);
+    if (backward)
+      return for_chunks(
+          chunks, [&](auto f) { return run_rows<k_score_bwd<T, f.nch, f.r>, f.r>(a, q, "k_score_bwd", nullptr); },
+          [&] { return run_rows<k_score_bwd_long<T>, 1>(a, q, "k_score_bwd_long", nullptr); });
+    return with_trunc(trunc, [&](auto tr) {
+      return for_chunks(
+          chunks,
+          [&](auto f) { return run_rows<k_score<T, f.nch, f.r, decltype(tr)::value>, f.r>(a, q, "k_score", nullptr); },
+          [&] { return run_rows<k_score_long<T>, 1>(a, q, "k_score_long", nullptr); });
+    });
+  });
+}
+
+// The checks both scoring directions share (before any HIP call), and the arguments they share.
 int check_score(const char* fn, const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
-                const void* ref_logits, int64_t rsb, int64_t rsk, float temperature, int top_k, float top_p,
-                const int64_t* tokens, int S, bool* trunc) {
+                const void* ref_logits, int64_t rsb, int64_t rsk, float temperature, int& top_k, float top_p,
+                const int64_t* tokens, int S, bool& trunc) {
   BEAST_TRY(check_common(fn, logits, dtype, B, K, V, sb, sk, temperature));
   BEAST_REQUIRE(ref_logits == nullptr || (rsb >= 0 && rsk >= 0), "%s: strides must be >= 0 (rsb=%lld, rsk=%lld)", fn,
                 (long long)rsb, (long long)rsk);
-  BEAST_REQUIRE(top_k >= 0, "%s: top_k must be >= 0 (got %d)", fn, top_k);
-  BEAST_REQUIRE(top_p > 0.0f && top_p <= 1.0f, "%s: top_p must lie in (0, 1] (got %g)", fn, (double)top_p);
-  BEAST_REQUIRE(S >= 0 && S <= SAMPLE_MAX_S, "%s: S must lie in [0, %d] (got %d)", fn, SAMPLE_MAX_S, S);
+  BEAST_TRY(check_truncation_ranges(fn, top_k, top_p, S, 0));
   BEAST_REQUIRE(S == 0 || tokens != nullptr, "%s: null tokens with S=%d", fn, S);
-  *trunc = (top_k > 0 && top_k < V) || top_p < 1.0f;
-  const int epl = dtype == BEAST_LOGITS_F32 ? ElemF32::EPL : ElemF16::EPL;
-  BEAST_REQUIRE_CODE(!*trunc || V <= LG_MAX_CHUNKS * 64 * epl, BEAST_E_UNSUPPORTED,
-                     "%s supports top_k / top_p for V <= %d of this dtype (V=%d)", fn, LG_MAX_CHUNKS * 64 * epl, V);
-  return BEAST_OK;
+  return check_truncation(fn, dtype, V, top_k, top_p, trunc);
 }
 
 ScoreArgs score_args(const void* logits, int64_t B, int K, int V, int64_t sb, int64_t sk, const void* ref_logits,
                      int64_t rsb, int64_t rsk, float temperature, int top_k, float top_p, const int64_t* tokens,
                      int S, int64_t tok_offset, int64_t ignore_index) {
-  ScoreArgs a{};
-  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  ScoreArgs a = row_args<ScoreArgs>(logits, B, K, V, sb, sk);
   a.ref = ref_logits; a.rsb = rsb; a.rsk = rsk; a.rK = folded_k(B, K, rsb, rsk);
   a.inv_tau = (float)(1.0 / (double)temperature);
-  a.top_k = (top_k > 0 && top_k < V) ? top_k : 0; a.top_p = top_p;
+  a.top_k = top_k; a.top_p = top_p;
   a.tok = tokens; a.S = S; a.tok_offset = tok_offset; a.ignore_index = ignore_index;
   return a;
-}
-
-int run_score_typed(int dtype, bool backward, const ScoreArgs& a, bool trunc, const Queue& q) {
-  switch (dtype) {
-    case BEAST_LOGITS_F32: return run_score<ElemF32>(backward, a, trunc, q);
-    case BEAST_LOGITS_F16: return run_score<ElemF16>(backward, a, trunc, q);
-    default: return run_score<ElemBF16>(backward, a, trunc, q);
-  }
 }
 
 }  // namespace
@@ -2134,30 +2125,21 @@ extern "C" int beast_sample_rows(const void* logits, int dtype, int64_t B, int K
                                  float temperature, int top_k, float top_p, const float* uniforms, int S,
                                  int64_t tok_offset, int64_t* tokens_out, float* logprob_out, int32_t* kept_out,
                                  void* stream) {
-  BEAST_TRY(check_common("beast_sample_rows", logits, dtype, B, K, V, sb, sk, temperature));
-  BEAST_REQUIRE(top_k >= 0, "beast_sample_rows: top_k must be >= 0 (got %d)", top_k);
-  BEAST_REQUIRE(top_p > 0.0f && top_p <= 1.0f, "beast_sample_rows: top_p must lie in (0, 1] (got %g)", (double)top_p);
-  BEAST_REQUIRE(S >= 1 && S <= SAMPLE_MAX_S, "beast_sample_rows: S must lie in [1, %d] (got %d)", SAMPLE_MAX_S, S);
-  BEAST_REQUIRE(uniforms != nullptr && tokens_out != nullptr, "beast_sample_rows: null pointer");
-  const bool trunc = (top_k > 0 && top_k < V) || top_p < 1.0f;
-  const int epl = dtype == BEAST_LOGITS_F32 ? ElemF32::EPL : ElemF16::EPL;
-  BEAST_REQUIRE_CODE(!trunc || V <= LG_MAX_CHUNKS * 64 * epl, BEAST_E_UNSUPPORTED,
-                     "beast_sample_rows supports top_k / top_p for V <= %d of this dtype (V=%d)",
-                     LG_MAX_CHUNKS * 64 * epl, V);
+  const char* fn = "beast_sample_rows";
+  bool trunc = false;
+  BEAST_TRY(check_common(fn, logits, dtype, B, K, V, sb, sk, temperature));
+  BEAST_TRY(check_truncation_ranges(fn, top_k, top_p, S, 1));
+  BEAST_REQUIRE(uniforms != nullptr && tokens_out != nullptr, "%s: null pointer", fn);
+  BEAST_TRY(check_truncation(fn, dtype, V, top_k, top_p, trunc));
   if (B == 0) return BEAST_OK;
-  SampleArgs a{};
-  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  SampleArgs a = row_args<SampleArgs>(logits, B, K, V, sb, sk);
   a.inv_tau = (float)(1.0 / (double)temperature);
-  a.top_k = (top_k > 0 && top_k < V) ? top_k : 0; a.top_p = top_p;
+  a.top_k = top_k; a.top_p = top_p;
   a.u = uniforms; a.S = S; a.tok_offset = tok_offset;
   a.tok = tokens_out; a.logprob = logprob_out; a.kept = kept_out;
   Queue q;
-  if (const int rc = queue_of(stream, q, "beast_sample_rows")) return rc;
-  switch (dtype) {
-    case BEAST_LOGITS_F32: return run_sample<ElemF32>(a, trunc, q);
-    case BEAST_LOGITS_F16: return run_sample<ElemF16>(a, trunc, q);
-    default: return run_sample<ElemBF16>(a, trunc, q);
-  }
+  if (const int rc = queue_of(stream, q, fn)) return rc;
+  return run_sample(dtype, a, trunc, q);
 }
 
 extern "C" int beast_score_rows(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
@@ -2168,7 +2150,7 @@ extern "C" int beast_score_rows(const void* logits, int dtype, int64_t B, int K,
   const char* fn = "beast_score_rows";
   bool trunc = false;
   BEAST_TRY(check_score(fn, logits, dtype, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
-                        &trunc));
+                        trunc));
   BEAST_REQUIRE(logprob_out || entropy_out || kl_out || kept_out || stats_out, "%s: no output requested", fn);
   BEAST_REQUIRE(logprob_out == nullptr || S >= 1, "%s: logprob_out needs S >= 1", fn);
   BEAST_REQUIRE(kl_out == nullptr || ref_logits != nullptr, "%s: kl_out needs ref_logits", fn);
@@ -2178,7 +2160,7 @@ extern "C" int beast_score_rows(const void* logits, int dtype, int64_t B, int K,
   a.logprob = logprob_out; a.entropy = entropy_out; a.kl = kl_out; a.kept = kept_out; a.stats = stats_out;
   Queue q;
   if (const int rc = queue_of(stream, q, fn)) return rc;
-  return run_score_typed(dtype, false, a, trunc, q);
+  return run_score(dtype, false, a, trunc, q);
 }
 
 extern "C" int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
@@ -2190,7 +2172,7 @@ extern "C" int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, in
   const char* fn = "beast_score_rows_bwd";
   bool trunc = false;
   BEAST_TRY(check_score(fn, logits, dtype, B, K, V, sb, sk, ref_logits, rsb, rsk, temperature, top_k, top_p, tokens, S,
-                        &trunc));
+                        trunc));
   BEAST_REQUIRE(stats && grad_logits, "%s: null pointer", fn);
   BEAST_REQUIRE(grad_logprob || grad_entropy || grad_kl, "%s: no upstream gradient given", fn);
   BEAST_REQUIRE(grad_logprob == nullptr || S >= 1, "%s: grad_logprob needs S >= 1", fn);
@@ -2204,7 +2186,7 @@ extern "C" int beast_score_rows_bwd(const void* logits, int dtype, int64_t B, in
   a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk; a.gK = folded_k(B, K, gsb, gsk);
   Queue q;
   if (const int rc = queue_of(stream, q, fn)) return rc;
-  return run_score_typed(dtype, true, a, trunc, q);
+  return run_score(dtype, true, a, trunc, q);
 }
 
 extern "C" int beast_logits_expect(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
@@ -2213,13 +2195,12 @@ extern "C" int beast_logits_expect(const void* logits, int dtype, int64_t B, int
   BEAST_TRY(check_common("beast_logits_expect", logits, dtype, B, K, V, sb, sk, temperature));
   BEAST_REQUIRE(mean_out || argmax_out || stats_out, "beast_logits_expect: no output requested");
   if (B == 0) return BEAST_OK;
-  LogitsArgs a{};
-  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  LogitsArgs a = row_args<LogitsArgs>(logits, B, K, V, sb, sk);
   a.inv_tau = (float)(1.0 / (double)temperature); a.vm1 = (float)(V - 1); a.tok_offset = tok_offset;
   a.mean = mean_out; a.amax = argmax_out; a.stats = stats_out;
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_logits_expect")) return rc;
-  return run_typed(dtype, false, a, q, nullptr);
+  return run_expect(dtype, false, a, q, nullptr);
 }
 
 extern "C" int beast_logits_expect_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
@@ -2231,15 +2212,14 @@ extern "C" int beast_logits_expect_bwd(const void* logits, int dtype, int64_t B,
   BEAST_REQUIRE(gsb >= 0 && gsk >= V, "beast_logits_expect_bwd: grad_logits rows must not overlap (gsb=%lld, "
                 "gsk=%lld, V=%d)", (long long)gsb, (long long)gsk, V);
   if (B == 0) return BEAST_OK;
-  LogitsArgs a{};
-  a.logits = logits; a.sb = sb; a.sk = sk; a.rows = B * K; a.K = folded_k(B, K, sb, sk); a.V = V;
+  LogitsArgs a = row_args<LogitsArgs>(logits, B, K, V, sb, sk);
   a.gK = folded_k(B, K, gsb, gsk);
   a.inv_tau = (float)(1.0 / (double)temperature); a.vm1 = (float)(V - 1);
   a.mean = const_cast<float*>(mean); a.stats = const_cast<float*>(stats);
   a.grad_mean = grad_mean; a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk;
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_logits_expect_bwd")) return rc;
-  return run_typed(dtype, true, a, q, nullptr);
+  return run_expect(dtype, true, a, q, nullptr);
 }
 
 extern "C" int64_t beast_logits_resident_rows(int dtype, int V, int backward, void* stream) {
@@ -2252,7 +2232,7 @@ extern "C" int64_t beast_logits_resident_rows(int dtype, int V, int backward, vo
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_logits_resident_rows")) return rc;
   int64_t rows = 0;
-  if (const int rc = run_typed(dtype, backward != 0, a, q, &rows)) return rc;
+  if (const int rc = run_expect(dtype, backward != 0, a, q, &rows)) return rc;
   return rows;
 }
 
@@ -2267,7 +2247,7 @@ extern "C" int beast_xent_rows(const void* logits, int dtype, int64_t B, int K, 
   a.loss = loss_out; a.stats = stats_out; a.amax = argmax_out;
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_xent_rows")) return rc;
-  return run_xent_typed(dtype, false, a, q);
+  return run_xent(dtype, false, a, q);
 }
 
 extern "C" int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int K, int V, int64_t sb, int64_t sk,
@@ -2285,5 +2265,5 @@ extern "C" int beast_xent_rows_bwd(const void* logits, int dtype, int64_t B, int
   a.stats = const_cast<float*>(stats); a.grad_loss = grad_loss; a.grad = grad_logits; a.gsb = gsb; a.gsk = gsk;
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_xent_rows_bwd")) return rc;
-  return run_xent_typed(dtype, true, a, q);
+  return run_xent(dtype, true, a, q);
 }

@@ -17,10 +17,7 @@ read and the gradient written plus the per-row inputs (backward).  The gate: eac
 slowest repeat is faster than its ATen counterpart's fastest at every batch size and dtype
 (``gate_fused_below_aten``).
 
-``--rows R`` sets BEAST_DEBUG_LOGITS_ROWS (rows a wave works on at once: 1, 2 or 4) before the
-library is loaded: the measurement behind the default.
-
-    python tests/tools/logits_timing.py [--rows R] [--out FILE.json]
+    python tests/tools/logits_timing.py [--out FILE.json]
 
 Needs a GPU; prints one JSON line.
 """
@@ -48,11 +45,8 @@ def main():
     ap.add_argument("--dtypes", nargs="+", default=list(DTYPES), choices=list(DTYPES))
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--window-ms", type=float, default=30.0)
-    ap.add_argument("--rows", type=int, default=None, choices=[1, 2, 4])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.rows is not None:
-        os.environ["BEAST_DEBUG_LOGITS_ROWS"] = str(args.rows)
     from beast_tokenizer_amd import _lib
     if not torch.cuda.is_available():
         raise SystemExit("logits_timing.py needs a GPU: nothing is measured without one")
@@ -147,7 +141,7 @@ def main():
             torch.cuda.empty_cache()
     gate = all(r["gate_fused_below_aten"] for r in results)
     line = json.dumps({"tool": "logits_timing", "shape": {"K": K, "V": V, "temperature": TAU},
-                       "rows_per_wave": args.rows or "default", "device": torch.cuda.get_device_name(0),
+                       "device": torch.cuda.get_device_name(0),
                        "results": results, "gate_fused_below_aten": gate})
     print(line)
     if args.out:

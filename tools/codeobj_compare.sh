@@ -6,10 +6,12 @@
 # (which carries paths) are not compared.  A unit that differs is disassembled on both sides and
 # listed per kernel symbol: same / DIFFERENT by instruction text alone (addresses, encodings and
 # branch targets stripped), with the VGPR / SGPR / LDS / scratch of both builds beside a kernel
-# that differs.                                bash tools/codeobj_compare.sh REV
+# that differs.  Units that exist on one side only (a unit that was split, merged or renamed) are
+# compared the same way per kernel symbol, all of them together: same / DIFFERENT / only in the
+# old / only in the new build.                 bash tools/codeobj_compare.sh REV
 set -eu
 REV="$1"; R="$(cd "$(dirname "$0")/.." && pwd)"; W=/tmp/codeobj_wt_$$; O=/tmp/codeobj_o_$$
-B=/opt/rocm/lib/llvm/bin
+B=/opt/rocm/lib/llvm/bin; N="$R/beast_tokenizer_amd/csrc/build"
 git -C "$R" worktree add -q "$W" "$REV"
 mkdir -p "$O"
 (cd "$W" && python3 - "$O" <<'PY'
@@ -21,47 +23,46 @@ for src in _build._sources():
                     "-o", os.path.join(sys.argv[1], os.path.basename(src)[:-4] + ".o")], check=True)
 PY
 )
-for o in "$O"/*.o; do
-  f=$(basename "$o" .o); n="$R/beast_tokenizer_amd/csrc/build/$f.o"
-  [ -f "$n" ] || { echo "$f: not in the current build"; continue; }
-  r=""
-  for w in old new; do
-    src=$([ $w = old ] && echo "$o" || echo "$n")
-    $B/llvm-objcopy --dump-section=.hip_fatbin="$O/$w.fatbin" "$src" 2>/dev/null || { r=" no device code"; break; }
-    $B/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input="$O/$w.fatbin" --output="$O/$w.co" --unbundle
-    for s in .text .rodata; do $B/llvm-objcopy --dump-section=$s="$O/$w$s" "$O/$w.co"; done
-  done
-  if [ -z "$r" ]; then for s in .text .rodata; do cmp -s "$O/old$s" "$O/new$s" && r="$r $s same" || r="$r $s DIFFERENT"; done; fi
-  echo "$f:$r"
-  case "$r" in *DIFFERENT*) python3 - "$B" "$O/old.co" "$O/new.co" <<'PY'
+# code_object OBJ OUT.co: the gfx950 code object of a unit; fails where the unit has no device code
+code_object() {
+  $B/llvm-objcopy --dump-section=.hip_fatbin="$2.fatbin" "$1" 2>/dev/null || return 1
+  $B/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input="$2.fatbin" --output="$2" --unbundle
+}
+# per_kernel "OLD.co ..." "NEW.co ...": the kernels of the code objects of each side, per symbol
+per_kernel() {
+  python3 - "$B" "$1" "$2" <<'PY'
 import re, subprocess, sys
-B, old, new = sys.argv[1:4]
+B, old, new = sys.argv[1], sys.argv[2].split(), sys.argv[3].split()
 
 
-def kernels(co):
+def kernels(cos):
     """symbol -> its instructions as text: no addresses, no encodings, no branch targets"""
     out, cur = {}, None
-    dis = subprocess.run([B + "/llvm-objdump", "-d", co], capture_output=True, text=True, check=True).stdout
-    for line in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if m:
-            cur = out.setdefault(m.group(1), [])
-        elif cur is not None and line.startswith("\t"):
-            ins = line.split("//")[0].strip()
-            cur.append(ins.split()[0] if re.match(r"s_c?branch", ins) else ins)
+    for co in cos:
+        dis = subprocess.run([B + "/llvm-objdump", "-d", co], capture_output=True, text=True, check=True).stdout
+        for line in dis.splitlines():
+            m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+            if m:
+                cur = out.setdefault(m.group(1), [])
+            elif cur is not None and line.startswith("\t"):
+                ins = line.split("//")[0].strip()
+                if ins == "...":   # zero padding behind a function's last instruction
+                    continue
+                cur.append(ins.split()[0] if re.match(r"s_c?branch", ins) else ins)
     return out
 
 
-def resources(co):
+def resources(cos):
     """kernel symbol -> the descriptor fields that matter, from the code object's metadata note"""
-    note = subprocess.run([B + "/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
     res = {}
-    for blk in re.split(r"\n\s+- \.agpr_count:", note)[1:]:
-        f = dict(re.findall(r"\.(name|vgpr_count|sgpr_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\S+)",
-                            blk))
-        res[f.get("name")] = "vgpr %s sgpr %s lds %s scratch %s" % (
-            f.get("vgpr_count"), f.get("sgpr_count"), f.get("group_segment_fixed_size"),
-            f.get("private_segment_fixed_size"))
+    for co in cos:
+        note = subprocess.run([B + "/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+        for blk in re.split(r"\n\s+- \.agpr_count:", note)[1:]:
+            f = dict(re.findall(
+                r"\.(name|vgpr_count|sgpr_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\S+)", blk))
+            res[f.get("name")] = "vgpr %s sgpr %s lds %s scratch %s" % (
+                f.get("vgpr_count"), f.get("sgpr_count"), f.get("group_segment_fixed_size"),
+                f.get("private_segment_fixed_size"))
     return res
 
 
@@ -74,8 +75,37 @@ for k in names:
         print("    %s: same" % k)
     else:
         print("    %s: DIFFERENT (%d -> %d instructions; old %s; new %s)" % (k, len(ko[k]), len(kn[k]), ro.get(k), rn.get(k)))
-print("    %d of %d kernels same" % (sum(1 for k in names if ko.get(k) == kn.get(k)), len(names)))
+print("    %d of %d kernels same, %d only in the old build, %d only in the new build" % (
+    sum(1 for k in names if ko.get(k) == kn.get(k)), len(names), sum(1 for k in names if k not in kn),
+    sum(1 for k in names if k not in ko)))
 PY
-  ;; esac
+}
+UO=""; UN=""; unpaired=""
+for o in "$O"/*.o; do
+  f=$(basename "$o" .o); n="$N/$f.o"
+  if [ ! -f "$n" ]; then
+    unpaired="$unpaired old:$f"
+    if code_object "$o" "$O/old_$f.co"; then UO="$UO $O/old_$f.co"; fi
+    continue
+  fi
+  r=""
+  for w in old new; do
+    src=$([ $w = old ] && echo "$o" || echo "$n")
+    code_object "$src" "$O/$w.co" || { r=" no device code"; break; }
+    for s in .text .rodata; do $B/llvm-objcopy --dump-section=$s="$O/$w$s" "$O/$w.co"; done
+  done
+  if [ -z "$r" ]; then for s in .text .rodata; do cmp -s "$O/old$s" "$O/new$s" && r="$r $s same" || r="$r $s DIFFERENT"; done; fi
+  echo "$f:$r"
+  case "$r" in *DIFFERENT*) per_kernel "$O/old.co" "$O/new.co";; esac
 done
+for src in "$R"/beast_tokenizer_amd/csrc/*.hip; do
+  f=$(basename "$src" .hip)
+  [ -f "$O/$f.o" ] && continue
+  unpaired="$unpaired new:$f"
+  if code_object "$N/$f.o" "$O/new_$f.co"; then UN="$UN $O/new_$f.co"; fi
+done
+if [ -n "$unpaired" ]; then
+  echo "units on one side only (${unpaired# }), per kernel:"
+  per_kernel "$UO" "$UN"
+fi
 git -C "$R" worktree remove --force "$W"; rm -rf "$O"
