@@ -563,6 +563,16 @@ class BEASTBsplineTokenizer(TokenizerBase):
                 dev = self._dev_of[idx] = torch.device("cuda", idx)
         return dev
 
+    _MAX_DOF = 64   # every kernel but the core codec's (k_encode_dof / k_reconstruct_dof: up to 256)
+
+    def _narrow_only(self, what: str) -> None:
+        """Refuse ``what`` on a wide action space, before any launch and before the device is asked for."""
+        if self.num_dof > self._MAX_DOF:
+            raise NotImplementedError(
+                f"{what} supports num_dof <= {self._MAX_DOF} (num_dof={self.num_dof}): at 65 <= num_dof <= 256 an "
+                "unconditioned tokenizer encodes, fits its bounds, decodes and reconstructs positions without "
+                "grad on the default grid or a shared 1-D times grid; nothing else")
+
     def _plan(self) -> _Plan:
         # hot path: plain attribute / dict lookups only (nn.Module.__getattr__ on the buffers
         # costs ~0.3 us each, a large part of a B=4096 call)
@@ -573,6 +583,8 @@ class BEASTBsplineTokenizer(TokenizerBase):
                     and p.llm == self.llm_vocab_size and p.dkey is self.device
                     and (p.pinned or p.idx == torch.cuda.current_device())):
                 return p
+        if self._conditioned:   # no plan is ever cached for such a tokenizer: every call arrives here
+            self._narrow_only("a tokenizer with init_cond_order / end_cond_order != 0")
         dev = self._dev()
         p = self._plans.get(dev.index)
         if (p is None or p.version != self._times_version or p.wmin is not self.w_min or p.wmax is not self.w_max
@@ -897,7 +909,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         if not isinstance(x, torch.Tensor) or x.dim() != 3:
             return False
         p = self._plan()
-        streamed = self.num_basis > 16 or p.T > 256
+        streamed = self.num_basis > 16 or p.T > 256 or self.num_dof > self._MAX_DOF   # k_encode_dof streams too
         if self._conditioned and not streamed:
             return False
         if (x.device != p.dev or x.dtype is not torch.float32 or not x.is_contiguous() or x.shape[0] == 0
@@ -1042,6 +1054,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         """One launch of beast_encode_rows_f32 (csrc/fit_rows.hip): the weighted ridge fit of every
         trajectory on its own time stamps.  Returns (params, tokens or None, device).  The
         argument checks run before the device is asked for."""
+        self._narrow_only("encode_at / encode_continuous_at (per-trajectory times)")
         if self._basis.conditioned:
             raise NotImplementedError(
                 "encode_at supports init_cond_order = end_cond_order = 0 only: the conditions come from "
@@ -1145,6 +1158,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         """One launch of beast_encode_windows_f32 (csrc/windows.hip).  Returns (params, tokens or
         None, valid, tile counts or None, device).  The argument checks run before the device is
         asked for."""
+        self._narrow_only("encode_windows")
         if self._basis.conditioned:
             raise NotImplementedError(
                 "encode_windows supports init_cond_order = end_cond_order = 0 only: the conditions are kept "
@@ -1313,6 +1327,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
     def _blend_windows(self, tokens, ntokens, starts, ends, num_frames, blend, fill, offset: int, want_counts: bool):
         """One launch of beast_reconstruct_windows_f32 (csrc/blend.hip).  The argument checks run before
         the device is asked for."""
+        self._narrow_only("reconstruct_windows")
         if self._basis.conditioned:
             raise NotImplementedError(
                 "reconstruct_windows supports init_cond_order = end_cond_order = 0 only: the conditions are kept "
@@ -1493,6 +1508,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
             return phi, phi.data_ptr(), 0, Tn
         if t.dim() != 2 or t.shape[0] != B:
             raise ValueError(f"times must be [T] or [B, T]; got {tuple(t.shape)} for B={B}")
+        self._narrow_only("reconstruct on per-trajectory times")
         Tn = t.shape[1]
         phi_k = self._basis.basis_at(t)                       # [kinds, B, T, N]
         phi = torch.zeros((B, 2, Tn, N), dtype=torch.float32, device=dev)
@@ -1563,6 +1579,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
                 )
             params = params.to(torch.float32).contiguous()
             if grad:
+                self._narrow_only("the autograd path of reconstruct_traj_continuous")
                 ip = self._init_p_rows(init_p, params.shape[0], p)
                 return _ReconstructContinuous.apply(params, ip, self, p, times, None)[0]
             return self._reconstruct(None, params, times, init_p, False, p)
@@ -1647,6 +1664,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         With init / end conditions the last fit's conditions are used, as in ``reconstruct_traj``.
 
         No autograd graph is recorded: the outputs are written by the kernel into fresh tensors."""
+        self._narrow_only("reconstruct_traj_derivs")
         orders = self._check_orders(orders)
         p = self._plan()
         tokens = self._token_rows(tokens, p.dev)
@@ -1664,6 +1682,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         """``reconstruct_traj_derivs`` from normalised params in (t d) order (the
         ``reconstruct_traj_continuous`` input); kwargs: init_p [B, num_dof].  Differentiable as
         ``reconstruct_traj_continuous`` is: every requested order feeds the one backward launch."""
+        self._narrow_only("reconstruct_traj_continuous_derivs")
         orders = self._check_orders(orders)
         p = self._plan()
         init_p = kwargs.get("init_p")
@@ -2011,6 +2030,7 @@ class BEASTBsplineTokenizer(TokenizerBase):
         dtypes are cast to fp32.  Tokenizers with init / end conditions take the composed path
         (``encode`` + ``reconstruct_traj`` + torch reductions; ``encode`` stores the conditions as
         usual) and return ``mse_fit = None``."""
+        self._narrow_only("reconstruction_stats / evaluate_reconstruction")
         p = self._plan()
         trajs = torch.as_tensor(trajs)
         if trajs.device != p.dev or trajs.dtype is not torch.float32:

@@ -22,6 +22,9 @@
 //   codec_stream.h       k_encode_stream / k_encode_stream_list / k_reconstruct_wide: N up to 32, T up
 //                        to 4096, with the time axis streamed through LDS in chunks; their plans
 //                        (tile, chunk length)
+//   codec_wide_dof.h     k_encode_dof / k_reconstruct_dof: 65 <= D <= 256 DoFs, the work item a
+//                        (trajectory, DoF block), both operands streamed at every T; their plans
+//                        (blocks, chunk length)
 //
 // Which kernel a call gets is decided below (launch_encode, launch_reconstruct, the round-trip
 // dispatch in beast_roundtrip_stats_f32) and reported through BEAST_OPT_LAST_CODEC_LAUNCH.
@@ -39,12 +42,14 @@
 #include "codec_reconstruct.h"
 #include "codec_roundtrip.h"
 #include "codec_stream.h"
+#include "codec_wide_dof.h"
 
 namespace {
 
 // MAX_T / MAX_N: the resident kernels' envelope (and every other entry point's); beast_encode_f32,
 // beast_encode_list_f32 and beast_reconstruct_f32 go on to STREAM_MAX_T / STREAM_MAX_N through the
-// streamed kernels.
+// streamed kernels, and they and beast_quantize_f32 to WIDE_MAX_D (codec_wide_dof.h) DoFs through
+// k_encode_dof / k_reconstruct_dof.
 constexpr int MAX_T = 256;
 constexpr int MAX_N = 16;
 constexpr int MAX_D = 64;
@@ -179,6 +184,24 @@ int launch_encode_stream_list(EncArgs a, int T, int D, int nj, int N, const Queu
                 : launch<k_encode_stream_list<2, false>>(grid, ST_NT, L.total, q, "k_encode_stream_list", a, p.tbt, p.tc, a16);
 }
 
+// 65 <= D <= WIDE_MAX_D: k_encode_dof over (trajectory, DoF block) items, blocks by dof_plan, chunk by
+// wd_enc_chunk; list mode is the same kernel reading the pointer table.  Reported as the streamed
+// kernels are (runtime-shape family, staged = 0), tile 1; fast = unit element stride (whether a block
+// then goes by DMA is decided on the device, from dof_src).
+template <bool LIST>
+int launch_encode_dof(EncArgs a, int T, int D, int nj, int N, const Queue& q) {
+  const DofPlan p = dof_plan(D, nj);
+  const int nk = nj < D ? 2 : 1, tc = wd_enc_chunk(N, nk);
+  a.g = make_geom<1>(D, nj, N, T);
+  a.ntiles = a.B * p.nblk;
+  const WeSmem L = wd_enc_smem(tc, p.bd, N, N <= 16 ? 16 : 32, nk, p.nblk);
+  BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "wide-DoF encode item needs %d B of LDS", L.total);
+  const unsigned grid = (unsigned)grid_for(a.ntiles, L.total, q.dev);
+  mark_launch(launch_mark(FAM_ENCODE_DYN, 1, ST_NW, 0, a.sd == 1, false, false, false));
+  return N <= 16 ? launch<k_encode_dof<1, LIST>>(grid, ST_NT, L.total, q, "k_encode_dof", a, p.nblk, p.bd, tc)
+                 : launch<k_encode_dof<2, LIST>>(grid, ST_NT, L.total, q, "k_encode_dof", a, p.nblk, p.bd, tc);
+}
+
 int enc_smem_total(int tbt, int T, int Dl, int D, int N, int nkinds) {
   const int Tp = round_up(T, 4);
   switch (tbt) {
@@ -196,6 +219,7 @@ int enc_smem_total(int tbt, int T, int Dl, int D, int N, int nkinds) {
 // The BEAST default shapes (T = 50, N = 10, D = 14 with 0 or 2 gripper DoF, D = 7) run fully
 // specialised kernels.
 int launch_encode(EncArgs a, int T, int D, int nj, int N, const Queue& q) {
+  if (D > MAX_D) return launch_encode_dof<false>(a, T, D, nj, N, q);
   if (N > MAX_N || T > MAX_T) return launch_encode_stream(a, T, D, nj, N, q);
   const int64_t traj_bytes = (int64_t)T * a.row_elems * 4;
   const bool contiguous = a.sd == 1 && a.st == a.row_elems && a.sb == (int64_t)T * a.row_elems &&
@@ -338,6 +362,29 @@ int launch_reconstruct_wide(RecArgs a, int D, int nj, int N, const Queue& q) {
   }
 }
 
+// 65 <= D <= WIDE_MAX_D on a shared basis (or decode-only): k_reconstruct_dof over (trajectory, DoF
+// block) items, row chunk by wd_rec_rows.  Reported as k_reconstruct_wide is (ks = 0), tile 1.
+int launch_reconstruct_dof(RecArgs a, int D, int nj, int N, const Queue& q) {
+  const DofPlan p = dof_plan(D, nj);
+  const int nk = nj < D ? 2 : 1, rc = wd_rec_rows(N, nk);
+  a.g = make_geom<1>(D, nj, N, 1);
+  a.tbt = 1;
+  a.ntiles = a.B * p.nblk;
+  const WrSmem L = wd_rec_smem(rc, p.bd, D, N, a.ndo, nk, a.pos_out != nullptr);
+  BEAST_REQUIRE_CODE(L.total <= 160 * 1024, BEAST_E_UNSUPPORTED, "wide-DoF reconstruct item needs %d B of LDS", L.total);
+  const unsigned grid = (unsigned)grid_for(a.ntiles, L.total, q.dev);
+  const float rinv = 1.0f / (float)(a.vocab - 1);   // IEEE division: beast::exact_quotient's r
+  mark_launch(launch_mark(FAM_REC_MFMA, 1, ST_NW, 0, false, false, true, false));
+#define BEAST_REC_DOF_CASE(K) \
+  case K: return launch<k_reconstruct_dof<K>>(grid, ST_NT, L.total, q, "k_reconstruct_dof", a, p.nblk, p.bd, rc, rinv);
+  switch ((N + 3) / 4) {
+    BEAST_REC_DOF_CASE(1) BEAST_REC_DOF_CASE(2) BEAST_REC_DOF_CASE(3) BEAST_REC_DOF_CASE(4)
+    BEAST_REC_DOF_CASE(5) BEAST_REC_DOF_CASE(6) BEAST_REC_DOF_CASE(7) BEAST_REC_DOF_CASE(8)
+  }
+#undef BEAST_REC_DOF_CASE
+  return BEAST_OK;   // unreachable: 1 <= N <= 32
+}
+
 template <class S, int WF>
 int launch_roundtrip(const float* traj, int64_t B, RtArgs a, int W, const Queue& q) {
   const RtSmem L = rt_smem(a.T, a.D, a.N, a.nj < a.D ? 2 : 1, W, a.lut_n);
@@ -366,7 +413,7 @@ extern "C" int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb,
   BEAST_REQUIRE(T >= 1 && N >= 1, "beast_encode_f32: seq_len T=%d and num_basis N=%d must be >= 1", T, N);
   BEAST_REQUIRE_CODE(T <= STREAM_MAX_T && N <= STREAM_MAX_N, BEAST_E_UNSUPPORTED,
                      "beast_encode_f32 supports T <= %d, N <= %d (T=%d N=%d)", STREAM_MAX_T, STREAM_MAX_N, T, N);
-  BEAST_REQUIRE(D >= 1 && D <= MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
+  BEAST_REQUIRE(D >= 1 && D <= WIDE_MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
   BEAST_REQUIRE(row_elems >= 1, "row_elems must be >= 1");
   BEAST_REQUIRE(!tokens_out || (w_min && w_max && vocab >= 2), "quantisation needs w_min/w_max and vocab >= 2");
   BEAST_REQUIRE(B >= 0, "batch size B=%lld must be >= 0", (long long)B);
@@ -388,8 +435,8 @@ extern "C" int beast_encode_list_f32(const float* const* traj_list, int nbatch, 
   BEAST_REQUIRE(rows_per_batch % 8 == 0, "rows_per_batch=%lld is not a multiple of 8", (long long)rows_per_batch);
   BEAST_REQUIRE(T >= 1 && T <= STREAM_MAX_T, "seq_len T=%d outside [1, %d]", T, STREAM_MAX_T);
   BEAST_REQUIRE(N >= 1 && N <= STREAM_MAX_N, "num_basis N=%d outside [1, %d]", N, STREAM_MAX_N);
-  BEAST_REQUIRE(D >= 1 && D <= MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
-  const bool streamed = N > MAX_N || T > MAX_T;   // k_encode_stream_list: any row length, 4-byte DMA units if need be
+  BEAST_REQUIRE(D >= 1 && D <= WIDE_MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
+  const bool streamed = N > MAX_N || T > MAX_T || D > MAX_D;   // k_encode_stream_list / k_encode_dof: any row length
   BEAST_REQUIRE(row_elems >= 1 && (streamed || ((int64_t)T * row_elems) % 4 == 0),
                 "beast_encode_list_f32: T*row_elems must be a multiple of 4");
   if (nbatch == 0 || rows_per_batch == 0) return BEAST_OK;
@@ -400,6 +447,7 @@ extern "C" int beast_encode_list_f32(const float* const* traj_list, int nbatch, 
   a.params_out = params_out;
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_encode_list_f32")) return rc;
+  if (D > MAX_D) return launch_encode_dof<true>(a, T, D, n_joint, N, q);
   if (streamed) return launch_encode_stream_list(a, T, D, n_joint, N, q);
   return launch_encode(a, T, D, n_joint, N, q);
 }
@@ -418,7 +466,10 @@ extern "C" int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, in
   BEAST_REQUIRE_CODE(N <= MAX_N || basis_sb == 0 || !pos_out, BEAST_E_UNSUPPORTED,
                      "beast_reconstruct_f32: per-trajectory bases stop at N = %d (N=%d): N up to %d needs a shared "
                      "basis (basis_sb = 0)", MAX_N, N, STREAM_MAX_N);
-  BEAST_REQUIRE(D >= 1 && D <= MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
+  BEAST_REQUIRE(D >= 1 && D <= WIDE_MAX_D && n_joint >= 0 && n_joint <= D, "bad DoF split D=%d n_joint=%d", D, n_joint);
+  BEAST_REQUIRE_CODE(D <= MAX_D || basis_sb == 0 || !pos_out, BEAST_E_UNSUPPORTED,
+                     "beast_reconstruct_f32: per-trajectory bases stop at D = %d (D=%d): D up to %d needs a shared "
+                     "basis (basis_sb = 0)", MAX_D, D, WIDE_MAX_D);
   BEAST_REQUIRE(vocab >= 2 || ntokens, "vocab must be >= 2");
   BEAST_REQUIRE(!pos_out || (basis && dof_dst && T_out >= 1 && T_out <= 4096 && num_dof_out >= D &&
                              num_dof_out <= 4096),
@@ -434,6 +485,7 @@ extern "C" int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, in
   const bool shared = (basis_sb == 0);
   Queue q;
   if (const int rc = queue_of(stream, q, "beast_reconstruct_f32")) return rc;
+  if (D > MAX_D) return launch_reconstruct_dof(a, D, n_joint, N, q);
   if (N > MAX_N) return launch_reconstruct_wide(a, D, n_joint, N, q);
   return launch_reconstruct<8>(a, D, n_joint, N, shared, q);
 }
@@ -480,16 +532,20 @@ extern "C" int beast_roundtrip_stats_f32(const float* traj, int64_t B, int T, in
 }
 
 extern "C" int beast_encode_stream_chunk(int T, int D, int row_elems, int n_joint, int N, int contiguous) {
-  if (T < 1 || T > STREAM_MAX_T || N < 1 || N > STREAM_MAX_N || D < 1 || D > MAX_D || n_joint < 0 || n_joint > D ||
-      row_elems < 1 || (N <= MAX_N && T <= MAX_T))
+  if (T < 1 || T > STREAM_MAX_T || N < 1 || N > STREAM_MAX_N || D < 1 || D > WIDE_MAX_D || n_joint < 0 ||
+      n_joint > D || row_elems < 1)
     return 0;
+  if (D > MAX_D) return wd_enc_chunk(N, n_joint < D ? 2 : 1);   // k_encode_dof streams at every T
+  if (N <= MAX_N && T <= MAX_T) return 0;
   return enc_stream_plan(D, row_elems, n_joint, N, contiguous != 0).tc;
 }
 
 extern "C" int beast_reconstruct_stream_rows(int T_out, int D, int n_joint, int N, int num_dof_out) {
-  if (T_out < 1 || T_out > 4096 || N <= MAX_N || N > STREAM_MAX_N || D < 1 || D > MAX_D || n_joint < 0 ||
+  if (T_out < 1 || T_out > 4096 || N < 1 || N > STREAM_MAX_N || D < 1 || D > WIDE_MAX_D || n_joint < 0 ||
       n_joint > D || num_dof_out < D || num_dof_out > 4096)
     return 0;
+  if (D > MAX_D) return wd_rec_rows(N, n_joint < D ? 2 : 1);   // k_reconstruct_dof, at every N
+  if (N <= MAX_N) return 0;
   return rec_wide_plan(D, n_joint, N, num_dof_out).rc;
 }
 

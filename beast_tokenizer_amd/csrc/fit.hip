@@ -255,6 +255,8 @@ extern "C" int beast_quantize_f32(const float* params, int64_t B, int D, int N, 
                                   float* ntok_out, void* stream) {
   BEAST_REQUIRE(params && w_min && w_max, "beast_quantize_f32: null input pointer");
   BEAST_REQUIRE((mode == 0 && tokens_out && vocab >= 2) || (mode == 1 && ntok_out), "beast_quantize_f32: bad mode");
+  // the widest action space beast_encode_f32 fits (codec.hip's WIDE_MAX_D); the kernel indexes any D
+  BEAST_REQUIRE(D >= 1 && D <= 256 && N >= 1, "beast_quantize_f32: bad shape D=%d N=%d (1 <= D <= 256)", D, N);
   BEAST_REQUIRE(B >= 0, "batch size B=%lld must be >= 0", (long long)B);
   if (B == 0) return BEAST_OK;
   Queue q;

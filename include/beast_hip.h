@@ -150,8 +150,9 @@ int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, d
  *   params_out  [B][D*N] fp32 unclamped fit (params_dict['params']); nullable
  *   tokens_out  [B][N*D] int64 = round_half_even(clamp01((clamp(p)-wmin)/max(wmax-wmin,1e-8))*(vocab-1))
  *               + tok_offset; nullable.  vocab <= 0 disables quantisation.
- * Constraints: N <= 32, T <= 4096, D <= 64 (BEAST_E_UNSUPPORTED above; N < 1 or T < 1 is
- * BEAST_E_INVALID); every shape inside them encodes, at any strides and alignment.  Two envelopes:
+ * Constraints: N <= 32, T <= 4096 (BEAST_E_UNSUPPORTED above; N < 1 or T < 1 is BEAST_E_INVALID),
+ * D <= 256 (BEAST_E_INVALID above); every shape inside them encodes, at any strides and alignment.
+ * Three envelopes:
  *   N <= 16 and T <= 256   the resident kernels: a tile's trajectories and the whole projection sit
  *                          in LDS (16-byte aligned contiguous rows of at most 32 KB per trajectory
  *                          take the DMA path);
@@ -160,12 +161,20 @@ int beast_bspline_projection_f64(const float* basis, int T, int N, double reg, d
  *                          LDS-DMA, other layouts gathered).  Nothing past a trajectory's last sample
  *                          is read.  An output's summation order depends on (T, chunk) alone, so a
  *                          trajectory's params and tokens are the same bits alone or in any batch.
+ *   65 <= D <= 256         k_encode_dof, at every N and T above: the work item is a (trajectory, block
+ *                          of DoFs) pair, the DoFs cut in joint-then-gripper order into the fewest equal
+ *                          blocks of at most 8 MFMA column tiles, and both operands are always streamed,
+ *                          in chunks of beast_encode_stream_chunk() steps that depend on (N, kinds)
+ *                          alone: a DoF's params and tokens are the same bits in any block or batch.
+ *                          A block whose dof_src entries are an ascending run of a unit-stride row is
+ *                          read in place by LDS-DMA (16-byte units where aligned, else 4-byte); any
+ *                          other block, and every last partial chunk, is gathered.
  * A dof_src entry outside [0, row_elems) is caller error: rows read in place by DMA clamp it into
  * the row, gathered rows read it as 0.0 (on both envelopes), so the result then depends on the layout.
  * proj must be 16-byte aligned (its rows are fetched in 16-byte units; Tp is a multiple of 4).
  * On both, tokens_out is bitwise beast_quantize_f32 (mode 0) of params_out.  beast_encode_list_f32 has
- * the same two envelopes; every other entry point that fits (_rows, _windows,
- * beast_roundtrip_stats_f32) keeps N <= 16, T <= 256. */
+ * the same three envelopes; every other entry point that fits (_rows, _windows,
+ * beast_roundtrip_stats_f32) keeps N <= 16, T <= 256, D <= 64. */
 int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st, int64_t sd, int row_elems,
                      int D, int n_joint, const int32_t* dof_src, const float* proj, int N,
                      const float* w_min, const float* w_max, int vocab, int64_t tok_offset,
@@ -175,8 +184,8 @@ int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st
  * which fits every dataloader batch then takes quantiles): batch i's rows start at the
  * device pointer traj_list[i] (traj_list itself is a device array of nbatch pointers),
  * every batch has rows_per_batch (a multiple of 8) contiguous rows of [T][row_elems] fp32;
- * params_out [nbatch * rows_per_batch][D*N] (d n).  N <= 32, T <= 4096, D <= 64
- * (BEAST_E_INVALID outside), on beast_encode_f32's two envelopes:
+ * params_out [nbatch * rows_per_batch][D*N] (d n).  N <= 32, T <= 4096, D <= 256
+ * (BEAST_E_INVALID outside), on beast_encode_f32's three envelopes:
  *   N <= 16 and T <= 256   k_encode, as beast_encode_f32's contiguous rows: every batch pointer
  *                          16-byte aligned and T * row_elems a multiple of 4 (BEAST_E_INVALID else);
  *   beyond either          k_encode_stream_list: the streamed fit with the tile source taken from
@@ -184,6 +193,8 @@ int beast_encode_f32(const float* traj, int64_t B, int T, int64_t sb, int64_t st
  *                          Any row length; a batch pointer that is not 16-byte aligned, or
  *                          T * row_elems off a multiple of 4, costs 4-byte DMA units, nothing else.
  *                          The chunk is beast_encode_stream_chunk(.., contiguous = 1).
+ *   65 <= D <= 256         k_encode_dof reading the table (the same kernel, a template flag): any row
+ *                          length and alignment.
  * Same arithmetic in the same order as beast_encode_f32 on the same rows, on both envelopes, so
  * params are bitwise those of per-batch calls. */
 int beast_encode_list_f32(const float* const* traj_list, int nbatch, int64_t rows_per_batch, int T, int row_elems,
@@ -194,7 +205,9 @@ int beast_encode_list_f32(const float* const* traj_list, int nbatch, int64_t row
  * used by encode(update_bounds=True) after the bounds move (:415-420).
  * mode 0: tokens_out int64 [B][N*D] (continuous_to_discrete + offset);
  * mode 1: ntok_out fp32 [B][N*D] = normalize_tensor (beast/utils.py:29-35),
- *         the encode_continuous path (:430-450). */
+ *         the encode_continuous path (:430-450).
+ * One thread per element at any shape: 1 <= D <= 256 (beast_encode_f32's widest), N >= 1, else
+ * BEAST_E_INVALID. */
 int beast_quantize_f32(const float* params, int64_t B, int D, int N, const float* w_min, const float* w_max,
                        int vocab, int64_t tok_offset, int mode, int64_t* tokens_out, float* ntok_out, void* stream);
 
@@ -339,7 +352,15 @@ int beast_blend_member_host(int64_t start, int64_t end, int64_t R, int T, int64_
  * basis only (basis_sb == 0, or a params_out-only call), T_out <= 4096, by k_reconstruct_wide: the
  * basis moves through LDS in chunks of beast_reconstruct_stream_rows() output rows, staged there and
  * stored per chunk (16 rows of num_dof_out columns must fit LDS, num_dof_out <= 640 at worst, else BEAST_E_UNSUPPORTED).
- * BEAST_E_UNSUPPORTED: N > 32; N > 16 with basis_sb != 0 (per-trajectory bases stop at N = 16). */
+ * 65 <= D <= 256 (every N <= 32): a shared basis only, as above, by k_reconstruct_dof over (trajectory,
+ * block of DoFs) items.  A block's tokens are dequantised once into LDS; Phi moves through LDS in chunks
+ * of beast_reconstruct_stream_rows() rows; every output is one accumulator started at 0 and summed K
+ * ascending over ceil(N / 4) v_mfma_f32_16x16x4_f32, step ks covering n = 4 ks .. 4 ks + 3 (for N <= 16
+ * too: not the resident kernels' order).  A block stores only the columns its own dof_dst entries name
+ * (one scatter from the staged chunk); the columns dof_dst names nowhere are zeroed by block 0 alone.
+ * Any num_dof_out <= 4096.  D > 256 is BEAST_E_INVALID.
+ * BEAST_E_UNSUPPORTED: N > 32; N > 16 or D > 64 with basis_sb != 0 and pos_out (per-trajectory bases
+ * stop at N = 16 and at D = 64). */
 int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, int n_joint, int N, int vocab,
                           int64_t tok_offset, const float* w_min, const float* w_max,
                           const float* basis, int64_t basis_sb, int T_out,
@@ -352,11 +373,14 @@ int beast_reconstruct_f32(const int64_t* tokens, int64_t B, int D, int n_joint, 
  * beast_encode_stream_chunk: time steps per chunk of beast_encode_f32 for this shape, a positive
  * multiple of 4; `contiguous` != 0: unit element stride, rows of row_elems floats, trajectories of
  * T rows back to back (sd == 1, st == row_elems, sb == T * row_elems).  It depends on T only
- * through the envelope: 0 where a resident kernel serves the shape (N <= 16 and T <= 256) and for
- * arguments beast_encode_f32 rejects.
+ * through the envelope: 0 where a resident kernel serves the shape (N <= 16, T <= 256 and D <= 64) and
+ * for arguments beast_encode_f32 rejects (D > 256 among them).  At 65 <= D <= 256 it is k_encode_dof's
+ * chunk at every T and N, a function of N and of whether both kinds are present.
  * beast_reconstruct_stream_rows: output rows per chunk of beast_reconstruct_f32 on a shared basis, a
- * positive multiple of 16 that does not depend on T_out; 0 for N <= 16, for arguments
- * beast_reconstruct_f32 rejects and where 16 rows of num_dof_out columns do not fit LDS. */
+ * positive multiple of 16 that does not depend on T_out; 0 for N <= 16 at D <= 64, for arguments
+ * beast_reconstruct_f32 rejects (D > 256 among them) and where 16 rows of num_dof_out columns do not
+ * fit LDS.  At 65 <= D <= 256 it is k_reconstruct_dof's chunk at every N, a function of N and of
+ * whether both kinds are present (num_dof_out does not enter). */
 int beast_encode_stream_chunk(int T, int D, int row_elems, int n_joint, int N, int contiguous);
 int beast_reconstruct_stream_rows(int T_out, int D, int n_joint, int N, int num_dof_out);
 
